@@ -1,11 +1,18 @@
 """Training throughput of the N2N U-Net step on MI355X (BASELINE.json metric, config 1).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL)
 
 A step = noise synthesis + neighbour sub-sampling + no-grad UNet(256^2) + UNet(128^2) fwd/bwd
 + N2N loss + [RCCL all-reduce of the flat gradient] + Adam, on bs=64 patches per rank of
 synthetic 256x256x1 data (weak scaling: global batch = 64 * N).  Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline figures (metric, value,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed (the loss
+it returned, the gradient and the updated parameters) as DIR/<name>.npy; the inputs and the
+initial weights are seeded, so two builds can be compared array for array.  --full adds the
+legs that take runs of their own: the profiled step pair behind the roofline / per-shape /
+per-op figures, the eval-PSNR leg and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -373,6 +380,81 @@ def oracle_eval_psnr(flat, clean8, noisy8, in_nc=1):
     return float(eval_ref.psnr(eval_ref.quantize_full(pred), clean8))
 
 
+def profile_fields(recs, reps, peak, ms_step, ref_flops, mode_tag, bs, H, device, ft, bf, x6):
+    """--full: the result-line fields that come from the profiled step pair (step_profile):
+    executed FLOPs and step_tflops, the roofline of the dominant 3x3 launch, the per-op times"""
+    shapes, weighted, ms3, by_op, executed = per_shape_roofline(recs, reps, peak)
+    # the FLOPs the step's launches execute (the pair-pixel no-grad pass computes dec_conv1b
+    # and the head at half the pixels): what step_tflops divides; ref_flops is SURVEY 8d's
+    step_flops = executed if executed > 0 and not ft else ref_flops
+    if shapes:  # the dominant in-step 3x3 launch shape (largest time per step)
+        dom = shapes[0]
+        kms, kflops = dom["avg_launch_ms"], dom["flops_per_launch"]
+        kdesc = f"{dom['kernel']} {dom['op']} {dom['shape']} (in-step launch)"
+        traffic, traffic_src, traffic_by = pmc_step_traffic(dom, mode_tag)
+    else:  # no 3x3 launch recorded: the isolated 96->96 shape
+        timer = (time_dominant_kernel_bf16 if bf else
+                 time_dominant_kernel_x6 if x6 else time_dominant_kernel)
+        kms, kflops = timer(bs, H, H, device)
+        kdesc = "96->96 3x3 @%dx%dx%d, isolated launch" % (bs, H, H)
+        traffic, traffic_src, traffic_by = None, None, None
+    achieved = kflops / (kms * 1e-3) / 1e12
+    # the bound of the dominant launch: its arithmetic intensity (algorithmic FLOPs over the
+    # fp32 activations it must move) against the machine balance peak / 8 TB/s -- the bf16
+    # base's 3x3 convs (~217 FLOP/B against 312) are HBM-bound, the bf16x6 ones (52) are not
+    alg_bytes = shapes[0]["algorithmic_bytes_per_launch"] if shapes else None
+    hbm_bound = bool(alg_bytes) and kflops / alg_bytes < peak * 1e12 / (PEAK_HBM_GBS * 1e9)
+    return {
+        "step_tflops": round(step_flops / (ms_step * 1e-3) / 1e12, 2),
+        "step_frac_of_fp32_peak": round(step_flops / (ms_step * 1e-3) / 1e12 / PEAK_FP32_TFLOPS, 4),
+        "step_flops_executed": step_flops,
+        "roofline": {"bound": "hbm" if hbm_bound else "mfma",
+                     "kernel": kdesc + ("; bf16 MFMA" if bf else "; fp32 as 6 split-bf16 "
+                                        "products, peak = bf16 dense / 6" if x6 else "; fp32 MFMA"),
+                     **({"achieved": round(alg_bytes / (kms * 1e-3) / 1e9, 1), "peak": PEAK_HBM_GBS,
+                         "unit": "GB/s", "frac": round(alg_bytes / (kms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                         "mfma_achieved_tflops": round(achieved, 2), "mfma_peak_tflops": peak,
+                         "mfma_frac": round(achieved / peak, 4)} if hbm_bound else
+                        {"achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                         "frac": round(achieved / peak, 4)}),
+                     "traffic": traffic,
+                     "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                     "traffic_of": traffic_by,
+                     "algorithmic_bytes_per_launch": alg_bytes,
+                     "avg_launch_ms": round(kms, 4), "flops_per_launch": kflops,
+                     "weighted_frac": round(weighted, 4) if weighted else None,
+                     "weighted_over": "every 3x3 launch of the step (fwd, pair-pixel fwd, "
+                                      "data and weight gradients), time-weighted",
+                     "ms_3x3_per_step": round(ms3, 3),
+                     "per_shape": [{k: v for k, v in d.items()
+                                    if k != "algorithmic_bytes_per_launch" and not k.startswith("_")}
+                                   for d in shapes],
+                     "method": "one profiled step pair after the timed region, every launch "
+                               "bracketed by HIP events on its stream, single-stream "
+                               "(dn_profile_ops)"},
+        "step_breakdown_ms": by_op,
+    }
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all arrays of --dump-outputs together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as <dirname>/<name>.npy in float32.  An array over its share
+    of DUMP_BUDGET_BYTES is cut to a fixed sample of its flattened elements (sorted indices from
+    a seeded generator: the same elements on every run)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -393,9 +475,16 @@ def main():
                          "or fp32 operands on the fp32 matrix cores")
     ap.add_argument("--arch", choices=["UNet", "UNetImproved"], default="UNet",
                     help="network (train.py:305-313 / finetune.py --arch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs the headline figures do not "
+                         "need: a profiled step pair (roofline, per-shape and per-op figures), "
+                         "the eval-PSNR leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, grad, params) as "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-eval", action="store_true",
-                    help="skip the eval-PSNR leg (and the CPU baseline that shares its image): "
+                    help="--full: skip the eval-PSNR leg (and the CPU baseline that shares its image): "
                          "under rocprofv3 --pmc the profiled step pair is then the run's last launches")
     ap.add_argument("--breakdown", action="store_true", help="per-phase HIP-event timing (stderr)")
     args = ap.parse_args()
@@ -477,8 +566,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss_v = loss.cpu().tolist()
-    # one profiled pair of steps after the timed region, on EVERY rank (the step all-reduces)
-    recs, reps = step_profile(step)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before any further step moves the parameters
+        dump_outputs(args.dump_outputs, {"loss": loss, "grad": tr.grad, "params": tr.opt.params})
+    if args.full:
+        # one profiled pair of steps after the timed region, on EVERY rank (the step all-reduces)
+        recs, reps = step_profile(step)
 
     if args.breakdown and rank == 0 and args.mode == "n2n":
         breakdown(tr, clean, device)
@@ -494,29 +587,6 @@ def main():
             ref_flops = bs * (fwd_flops(H, H, C) + 3 * 864.0 * C * H * H)
         else:  # two fwd/bwd at full resolution
             ref_flops = bs * 2 * 3 * fwd_flops(H, H, C)
-        shapes, weighted, ms3, by_op, executed = per_shape_roofline(recs, reps, peak)
-        # the FLOPs the step's launches execute (the pair-pixel no-grad pass computes dec_conv1b
-        # and the head at half the pixels): what step_tflops divides; ref_flops is SURVEY 8d's
-        step_flops = executed if executed > 0 and not ft else ref_flops
-        if shapes:  # the dominant in-step 3x3 launch shape (largest time per step)
-            dom = shapes[0]
-            kms, kflops = dom["avg_launch_ms"], dom["flops_per_launch"]
-            kdesc = f"{dom['kernel']} {dom['op']} {dom['shape']} (in-step launch)"
-            mode_tag = ("bf16" if bf else args.mode) + ("_iunet" if iu else "") + \
-                (f"_c{C}" if C != 1 else "")
-            traffic, traffic_src, traffic_by = pmc_step_traffic(dom, mode_tag)
-        else:  # no 3x3 launch recorded: the isolated 96->96 shape
-            timer = (time_dominant_kernel_bf16 if bf else
-                     time_dominant_kernel_x6 if x6 else time_dominant_kernel)
-            kms, kflops = timer(bs, H, H, device)
-            kdesc = "96->96 3x3 @%dx%dx%d, isolated launch" % (bs, H, H)
-            traffic, traffic_src, traffic_by = None, None, None
-        achieved = kflops / (kms * 1e-3) / 1e12
-        # the bound of the dominant launch: its arithmetic intensity (algorithmic FLOPs over the
-        # fp32 activations it must move) against the machine balance peak / 8 TB/s -- the bf16
-        # base's 3x3 convs (~217 FLOP/B against 312) are HBM-bound, the bf16x6 ones (52) are not
-        alg_bytes = shapes[0]["algorithmic_bytes_per_launch"] if shapes else None
-        hbm_bound = bool(alg_bytes) and kflops / alg_bytes < peak * 1e12 / (PEAK_HBM_GBS * 1e9)
         model = "ImprovedUNet(n_feature=48)" if iu else "UNet(n_feature=48)"
         if iu and not ft:
             workload = (f"{args.mode} step with arch_unet.ImprovedUNet(n_feature=48, depth=4, noise=True) "
@@ -552,38 +622,15 @@ def main():
                        "global_batch": bs * world, "patch": [H, H, C], "parallelism": f"dp{world}",
                        "collective": (f"{dist.get_backend()} all_reduce(sum) of the flat gradient per step"
                                       if grouped else "none (single process)")},
-            "step_tflops": round(step_flops / (ms_step * 1e-3) / 1e12, 2),
-            "step_frac_of_fp32_peak": round(step_flops / (ms_step * 1e-3) / 1e12 / PEAK_FP32_TFLOPS, 4),
-            "step_flops_executed": step_flops, "step_flops_reference": ref_flops,
-            "roofline": {"bound": "hbm" if hbm_bound else "mfma",
-                         "kernel": kdesc + ("; bf16 MFMA" if bf else "; fp32 as 6 split-bf16 "
-                                            "products, peak = bf16 dense / 6" if x6 else "; fp32 MFMA"),
-                         **({"achieved": round(alg_bytes / (kms * 1e-3) / 1e9, 1), "peak": PEAK_HBM_GBS,
-                             "unit": "GB/s", "frac": round(alg_bytes / (kms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                             "mfma_achieved_tflops": round(achieved, 2), "mfma_peak_tflops": peak,
-                             "mfma_frac": round(achieved / peak, 4)} if hbm_bound else
-                            {"achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                             "frac": round(achieved / peak, 4)}),
-                         "traffic": traffic,
-                         "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                         "traffic_of": traffic_by,
-                         "algorithmic_bytes_per_launch": shapes[0]["algorithmic_bytes_per_launch"]
-                         if shapes else None,
-                         "avg_launch_ms": round(kms, 4), "flops_per_launch": kflops,
-                         "weighted_frac": round(weighted, 4) if weighted else None,
-                         "weighted_over": "every 3x3 launch of the step (fwd, pair-pixel fwd, "
-                                          "data and weight gradients), time-weighted",
-                         "ms_3x3_per_step": round(ms3, 3),
-                         "per_shape": [{k: v for k, v in d.items()
-                                        if k != "algorithmic_bytes_per_launch" and not k.startswith("_")}
-                                       for d in shapes],
-                         "method": "one profiled step pair after the timed region, every launch "
-                                   "bracketed by HIP events on its stream, single-stream "
-                                   "(dn_profile_ops)"},
-            "step_breakdown_ms": by_op,
+            "step_flops_reference": ref_flops,
             "loss": loss_v,
         }
-        if args.mode == "n2n" and C == 1 and not iu and not args.no_eval:
+        if args.full:
+            mode_tag = ("bf16" if bf else args.mode) + ("_iunet" if iu else "") + \
+                (f"_c{C}" if C != 1 else "")
+            rec.update(profile_fields(recs, reps, peak, ms_step, ref_flops, mode_tag, bs, H, device,
+                                      ft, bf, x6))
+        if args.full and args.mode == "n2n" and C == 1 and not iu and not args.no_eval:
             # "eval PSNR vs ref" (BASELINE metric): the trained weights denoise one 512x512 image
             # on the HIP path; the CPU leg runs the reference restatement on the same weights
             clean8, noisy8 = eval_image()
@@ -592,7 +639,7 @@ def main():
                            "image": "512x512 synthetic, gauss25, after the timed steps",
                            "noisy_psnr": round(float(10 * __import__("math").log10(
                                255.0 ** 2 / float(((noisy8.astype("f8") - clean8) ** 2).mean()))), 4)}
-        if not args.no_cpu_baseline and not args.no_eval and world == 1 and args.mode == "n2n" and C == 1 and not iu:
+        if args.full and not args.no_cpu_baseline and not args.no_eval and world == 1 and args.mode == "n2n" and C == 1 and not iu:
             rec["cpu_baseline"] = cpu_baseline()
             ref_ps = oracle_eval_psnr(net.flat_params, clean8, noisy8)
             rec["cpu_baseline"]["eval_psnr"] = round(ref_ps, 4)

@@ -53,7 +53,7 @@ def main():
             out[k]["per_launch_fetch"] = [round(a * 2048) for a in f]
             out[k]["per_launch_write"] = [round(b * 1024) for b in w]
     doc = {"method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes with "
-                     "--kernel-trace over `bench.py --steps 2 --warmup 1 --no-cpu-baseline` "
+                     "--kernel-trace over `bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-eval` "
                      "(tools/gpu_run.sh pmc); per-launch means over every dispatch of the kernel "
                      "(all its shapes); FETCH x2 gfx950 correction; per_launch_bytes in dispatch order "
                      "(DN_STEP_STREAMS=0: one stream, the launch order of dn_profile_ops)",

@@ -1,16 +1,17 @@
 #!/bin/bash
-# rocprofv3 kernel-trace + stats of a short bench run -> gpurun_out/prof/<tag>
+# rocprofv3 kernel-trace + stats of a short bench run -> $OUT/prof/<tag>
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
+cd "$(dirname "$0")/.."
 TAG=${1:-bench}
 shift || true
 export TMPDIR=/tmp
-mkdir -p gpurun_out/prof
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/$TAG -o run \
-  -- python3 bench.py --steps ${PROF_STEPS:-3} --warmup 1 --no-cpu-baseline "$@" > gpurun_out/prof/$TAG.log 2>&1
+OUT=${DN_OUT_DIR:-bench_out}  # where the logs and profiler output go
+mkdir -p $OUT/prof
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/$TAG -o run \
+  -- python3 bench.py --full --steps ${PROF_STEPS:-3} --warmup 1 --no-cpu-baseline "$@" > $OUT/prof/$TAG.log 2>&1
 rc=$?
 echo "rocprof rc=$rc"
-f=$(find gpurun_out/prof/$TAG -name '*kernel_stats.csv' | head -1)
+f=$(find $OUT/prof/$TAG -name '*kernel_stats.csv' | head -1)
 [ -n "$f" ] && python3 - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
