@@ -543,11 +543,9 @@ dn_status dn_conv2d_forward_bf16(const float* x, int x_stride, int N, int H, int
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = launch_pack_bf16(conv_fwd_view(w, Cin, 3), Cin, Cout, pack_ws, s);
   if (e == hipSuccess) {
-    FwdArgs a{};
-    a.in = x; a.in_stride = x_stride; a.in_off = 0; a.IHt = H; a.IWt = W;
-    a.N = N; a.OH = H; a.OW = W; a.K = Cin; a.NOUT = Cout;
+    FwdArgs a = fwd_args(View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cin, Cout,
+                         View{y, y_stride, 0}, OUT_NHWC);
     a.wp = static_cast<const float*>(pack_ws); a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-    a.out = y; a.out_stride = y_stride; a.out_off = 0; a.out_layout = OUT_NHWC;
     e = launch_fwd_bf16(a, s);
   }
   return hip_status(e, "dn_conv2d_forward_bf16");
@@ -575,12 +573,10 @@ dn_status dn_conv2d_forward_x6(const float* x, int x_stride, int N, int H, int W
                                  x_stride % 4 == 0 && Cin % 4 == 0 && y_stride % 4 == 0);
   hipError_t e = launch_pack_x6(conv_fwd_view(w, Cin, 3), Cin, Cout, 0, pack_ws, s, tail);
   if (e == hipSuccess) {
-    FwdArgs a{};
+    FwdArgs a = fwd_args(View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cin, Cout,
+                         View{y, y_stride, 0}, OUT_NHWC);
     a.x6_tail = tail;
-    a.in = x; a.in_stride = x_stride; a.in_off = 0; a.IHt = H; a.IWt = W;
-    a.N = N; a.OH = H; a.OW = W; a.K = Cin; a.NOUT = Cout;
     a.wp = static_cast<const float*>(pack_ws); a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-    a.out = y; a.out_stride = y_stride; a.out_off = 0; a.out_layout = OUT_NHWC;
     e = launch_fwd_x6(a, s);
   }
   return hip_status(e, "dn_conv2d_forward_x6");
@@ -602,16 +598,14 @@ dn_status dn_conv2d_backward_data_x6(const float* dz, int N, int H, int W, int C
                                  Cout % 4 == 0 && dx_stride % 4 == 0 && (!mask || mask_stride % 4 == 0));
   hipError_t e = launch_pack_x6(conv_dgrad_view(w, Cin, 3), Cout, Cin, zc, pack_ws, s, tail);
   if (e == hipSuccess) {
-    FwdArgs a{};
+    FwdArgs a = fwd_args(View{const_cast<float*>(dz), Cout, 0}, N, H, W, Cout, Cin,
+                         View{dx, dx_stride, 0}, OUT_NHWC);
     a.x6_tail = tail;
-    a.in = dz; a.in_stride = Cout; a.in_off = 0; a.IHt = H; a.IWt = W;
-    a.N = N; a.OH = H; a.OW = W; a.K = Cout; a.NOUT = Cin;
     a.zc = zc;
     a.wp = static_cast<const float*>(pack_ws);
     a.wp_z = zc ? x6_pack_elems(Cout, Cin, zc) / ((Cin + zc - 1) / zc) : 0;
     a.epi = mask ? EPI_MASK : (accumulate ? EPI_ACCUM : EPI_PLAIN);
-    a.out = dx; a.out_stride = dx_stride; a.out_off = 0; a.out_layout = OUT_NHWC;
-    a.mask = mask; a.mask_stride = mask_stride; a.mask_off = 0;
+    set_mask(a, View{const_cast<float*>(mask), mask_stride, 0});
     e = launch_fwd_x6(a, s);
   }
   return hip_status(e, "dn_conv2d_backward_data_x6");
@@ -694,10 +688,9 @@ dn_status dn_deconv2x2_forward_x6(const float* x, int N, int H, int W, const flo
     return fail(DN_ERR_ARG, "bad shape");
   if (dn_status st = need_pack(pack_ws, pack_bytes, dn_deconv2x2_x6_pack_size())) return st;
   hipStream_t s = (hipStream_t)stream;
-  FwdArgs a{};
-  a.in = x; a.in_stride = 96; a.in_off = 0; a.IHt = H; a.IWt = W;
-  a.N = N; a.OH = H; a.OW = W; a.K = 96; a.NOUT = 96; a.bias = b;
-  a.out = y; a.out_stride = y_stride; a.out_off = y_off;
+  FwdArgs a = fwd_args(View{const_cast<float*>(x), 96, 0}, N, H, W, 96, 96,
+                       View{y, y_stride, y_off}, OUT_UP2);
+  a.bias = b;
   if (!deconv_x6_ok(a)) return fail(DN_ERR_ARG, "shape outside the bf16x6 deconv kernel");
   hipError_t e = launch_pack_deconv_x6(w, pack_ws, s);
   if (e == hipSuccess) e = launch_deconv_x6(a, pack_ws, s);
@@ -711,11 +704,10 @@ dn_status dn_deconv2x2_backward_data_x6(const float* dy, int dy_stride, int N, i
   if (N < 1 || H < 1 || W < 1 || dy_stride < 96 || (dy_stride & 3)) return fail(DN_ERR_ARG, "bad shape");
   if (dn_status st = need_pack(pack_ws, pack_bytes, dn_deconv2x2_x6_pack_size())) return st;
   hipStream_t s = (hipStream_t)stream;
-  FwdArgs a{};
-  a.in = dy; a.in_stride = dy_stride; a.in_off = 0; a.IHt = 2 * H; a.IWt = 2 * W;
-  a.N = N; a.OH = H; a.OW = W; a.K = 96; a.NOUT = 96;
-  a.epi = mask ? EPI_MASK : EPI_PLAIN; a.mask = mask; a.mask_stride = 96; a.mask_off = 0;
-  a.out = dx; a.out_stride = 96; a.out_off = 0;
+  FwdArgs a = fwd_args(View{const_cast<float*>(dy), dy_stride, 0}, 2 * H, 2 * W, N, H, W, 96, 96,
+                       View{dx, 96, 0}, OUT_NHWC);
+  a.epi = mask ? EPI_MASK : EPI_PLAIN;
+  set_mask(a, View{const_cast<float*>(mask), 96, 0});
   if (!deconv_dgrad_x6_ok(a)) return fail(DN_ERR_ARG, "shape outside the bf16x6 deconv kernel");
   PackBatch b;
   b.j[b.n++] = pack_job_deconv_dgrad_x6(w, pack_ws);

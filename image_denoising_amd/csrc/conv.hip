@@ -1466,7 +1466,10 @@ hipError_t launch_wgrad1(int mode, const WgradArgs& a0, float* dwb, hipStream_t 
   a.wlayout = up2 ? 1 : 0;  // deconv weight (in, out, 2, 2): [ci][co] per parity
   const dim3 grid(sp, 1, z);
   hipError_t e;
-  if (x6 && wgrad1p_ok(a)) {
+  const bool p1 = x6 && wgrad1p_ok(a);
+  // head_gnb (g = nb, the gradient recomputed; nin_c's rows in hd_slab_c): k_wgrad1p only
+  if (a.head_gnb > 0 && !p1) return hipErrorInvalidValue;
+  if (p1) {
     e = launch_wgrad1p(a, sp, s, up2);
   } else {
     if (a.Cout == 96)

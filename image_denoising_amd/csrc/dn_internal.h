@@ -169,6 +169,32 @@ struct View {
   int off;
 };
 
+// The FwdArgs fields every forward-family launch shares (the rest zero): `in` holds ih x iw
+// pixels per image and K channels, `out` the oh x ow output domain and nout channels.  The two
+// extents differ only for the deconv data gradient (ih x iw = 2 oh x 2 ow).
+inline FwdArgs fwd_args(const View& in, int ih, int iw, int N, int oh, int ow, int K, int nout,
+                        const View& out, int layout) {
+  FwdArgs a{};
+  a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = ih; a.IWt = iw;
+  a.N = N; a.OH = oh; a.OW = ow; a.K = K; a.NOUT = nout;
+  a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = layout;
+  return a;
+}
+// ... with the input at the output's resolution (every launch but the deconv data gradient)
+inline FwdArgs fwd_args(const View& in, int N, int h, int w, int K, int nout, const View& out,
+                        int layout) {
+  return fwd_args(in, h, w, N, h, w, K, nout, out, layout);
+}
+// EPI_MASK's saved activation / EPI_BIAS_ADD's residual
+inline void set_mask(FwdArgs& a, const View& m) {
+  a.mask = m.p; a.mask_stride = m.stride; a.mask_off = m.off;
+}
+// the fused 2x2 max-pool's destination (pool_only: the full-resolution output is not stored)
+inline void set_pool(FwdArgs& a, const View& pool, int pool_only) {
+  a.pool_out = pool.p; a.pool_stride = pool.stride; a.pool_off = pool.off;
+  a.pool_only = pool_only;
+}
+
 // geometry of the packed per-chunk weight image of the forward-family kernel
 struct FwdGeom { int KC, TAPS, WNS, LW; };
 

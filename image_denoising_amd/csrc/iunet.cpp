@@ -135,13 +135,10 @@ hipError_t grun(int ksize, const View& in, int N, int H, int W, int K, const flo
                 hipStream_t s) {
   GGeom g;
   if (!ggeom(ksize, K, nout, g)) return hipErrorInvalidValue;
-  FwdArgs a{};
-  a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = H; a.IWt = W;
-  a.N = N; a.OH = H; a.OW = W; a.K = K; a.NOUT = nout;
+  FwdArgs a = fwd_args(in, N, H, W, K, nout, out, layout);
   a.wp = wp; a.wp_z = g.img;
   a.bias = bias; a.epi = epi;
-  a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = layout;
-  a.mask = aux.p; a.mask_stride = aux.stride; a.mask_off = aux.off;
+  set_mask(a, aux);
   a.zc = g.np;
   return launch_fwd_nt(g.gather, g.nt, a, s);
 }
@@ -163,15 +160,12 @@ static bool w6_views(const View& out, int layout, const View& aux, int nout) {
 hipError_t x6run(const View& in, int N, int H, int W, int K, const float* wp, int nout,
                  const float* bias, int epi, const View& out, int layout, const View& aux,
                  int tail, hipStream_t s) {
-  FwdArgs a{};
+  FwdArgs a = fwd_args(in, N, H, W, K, nout, out, layout);
   a.x6_tail = tail;
-  a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = H; a.IWt = W;
-  a.N = N; a.OH = H; a.OW = W; a.K = K; a.NOUT = nout;
   a.zc = x6_zc(nout);
   a.wp = wp; a.wp_z = a.zc ? x6_pack_elems(K, nout, a.zc) / ((nout + a.zc - 1) / a.zc) : 0;
   a.bias = bias; a.epi = epi;
-  a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = layout;
-  a.mask = aux.p; a.mask_stride = aux.stride; a.mask_off = aux.off;
+  set_mask(a, aux);
   return launch_fwd_x6(a, s);
 }
 
@@ -627,8 +621,8 @@ dn_status forward_body(const Ctx& c, const float* x, float* y) {
                                 prm + P.ne2.b, TE_SIGMOID, kNone, View{ws + p.sig, 0, 0}, 1, 1, s));
   }
   IU_RUN(c, launch_nchw_to_slice(x, N, C, H, W, ws + p.cf, 28, 24, 28, s));  // final concat input
-                                 // encoder
-                                 View xi = c.V(p.x0, 4);
+  // encoder
+  View xi = c.V(p.x0, 4);
   for (int i = 0; i < 4; ++i) {
     const ILevel& L = P.down[i];
     const int h = H >> i, w = W >> i, nf = L.conv.cout, FS = nf + 4 * GROWTH;
@@ -807,8 +801,8 @@ dn_status rdb_bwd(const Ctx& c, float* dprm, const IRdb& R, const IBlockBufs& b,
   if (dn_status st = wgrad_g(c, dprm, W_C1, R.lff, dr, c.V(b.F, FS), h, w)) return st;
   if (dn_status st = dgrad_g(c, R.lff, dr, h, w, FS, EPI_PLAIN, kNone, c.V(b.dF, FS))) return st;
   IU_RUN(c, launch_vadd(c.V(b.dF, FS), dr, npx, C, c.s));  // out = x + lff(...)
-                        for (int j = 3; j >= 0; --j) {
-                        const int o = C + GROWTH * j;
+  for (int j = 3; j >= 0; --j) {
+    const int o = C + GROWTH * j;
     const View dzj = c.V(b.dzj[j], GROWTH);
     IU_RUN(c, launch_vmask(dzj, c.V(b.dF, FS, o), c.V(b.F, FS, o), npx, GROWTH, c.s));
     if (dn_status st = wgrad_g(c, dprm, W_C3, R.conv[j], dzj, c.V(b.F, FS), h, w)) return st;
@@ -826,11 +820,7 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm, SideStream* 
   float* ws = c.ws;
   const hipStream_t s = c.s;
   const hipStream_t s2 = side ? side->st : s;
-  auto fork = [&]() -> hipError_t {
-    if (!side) return hipSuccess;
-    hipError_t e = hipEventRecord(side->fork, s);
-    return e != hipSuccess ? e : hipStreamWaitEvent(s2, side->fork, 0);
-  };
+  auto fork = [&] { return side_fork(side, s); };
   const IParams& P = p.P;
   const int N = p.N, H = p.H, W = p.W, C = P.C, OC = P.OC;
   const long HW = (long)H * W;
@@ -945,8 +935,7 @@ dn_status iunet_backward(const IPlan& p, const float* prm, const float* dy, floa
   // the launch that produced its output gradient; every buffer one reads (the forward's
   // activations, dz2 / dz1 / dr / dzf of a block, dzj[j], dps[k], dza[i], dzfin, dsg, dh once
   // written) is not rewritten later in the pass, and only they use the slab.  Joined at the end.
-  static const bool two_env = !getenv("DN_BWD_STREAMS") || atoi(getenv("DN_BWD_STREAMS")) != 0;
-  SideStream* side = two_env && !prof_on() && !g_prof.on ? side_stream(s) : nullptr;
+  SideStream* side = bwd_two_streams() && !prof_on() && !g_prof.on ? side_stream(s) : nullptr;
   PackBatch pb;
   long next = 0;
   Ctx c{p, prm, ws, s, prec};

@@ -325,37 +325,28 @@ hipError_t pack_deconv_dgrad(const float* w, int cout, int cin, float* out, hipS
 hipError_t conv_forward(const View& in, int N, int H, int W, int K, const float* wp,
                         const float* b, int cout, int ksize, int act, const View& out,
                         int out_layout, hipStream_t s) {
-  FwdArgs a{};
-  a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = H; a.IWt = W;
-  a.N = N; a.OH = H; a.OW = W; a.K = K; a.NOUT = cout;
-  a.wp = wp; a.wp_z = 0;
+  FwdArgs a = fwd_args(in, N, H, W, K, cout, out, out_layout);
+  a.wp = wp;
   a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-  a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = out_layout;
   return launch_fwd(ksize == 3 ? G_C3 : G_C1, a, s);
 }
 
 // dx (channels [0, nout)) from dz [N,H,W,cout]; wp = pack_conv_dgrad(...)
 hipError_t conv_dgrad(const View& dz, int N, int H, int W, int cout, const float* wp, int nout,
                       int ksize, int epi, const View& mask, const View& dx, hipStream_t s) {
-  FwdArgs a{};
-  a.in = dz.p; a.in_stride = dz.stride; a.in_off = dz.off; a.IHt = H; a.IWt = W;
-  a.N = N; a.OH = H; a.OW = W; a.K = cout; a.NOUT = nout;
-  a.wp = wp; a.wp_z = 0;
-  a.bias = nullptr; a.epi = epi;
-  a.out = dx.p; a.out_stride = dx.stride; a.out_off = dx.off; a.out_layout = OUT_NHWC;
-  a.mask = mask.p; a.mask_stride = mask.stride; a.mask_off = mask.off;
+  FwdArgs a = fwd_args(dz, N, H, W, cout, nout, dx, OUT_NHWC);
+  a.wp = wp;
+  a.epi = epi;
+  set_mask(a, mask);
   return launch_fwd(ksize == 3 ? G_C3 : G_C1, a, s);
 }
 
 // ConvTranspose2d(cin, cout, 2, 2): x [N,h,w,cin] -> out at (2y+a, 2x+b); wp = pack_deconv_fwd
 hipError_t deconv_forward(const View& x, int N, int h, int w, int cin, const float* wp,
                           const float* b, int cout, const View& out, hipStream_t s) {
-  FwdArgs a{};
-  a.in = x.p; a.in_stride = x.stride; a.in_off = x.off; a.IHt = h; a.IWt = w;
-  a.N = N; a.OH = h; a.OW = w; a.K = cin; a.NOUT = cout;
+  FwdArgs a = fwd_args(x, N, h, w, cin, cout, out, OUT_UP2);
   a.wp = wp; a.wp_z = pack_floats(G_UP, cout, cin, 1);
   a.bias = b; a.epi = EPI_BIAS;
-  a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = OUT_UP2;
   return launch_fwd(G_UP, a, s);
 }
 
@@ -363,13 +354,10 @@ hipError_t deconv_forward(const View& x, int N, int h, int w, int cin, const flo
 // wp = pack_deconv_dgrad
 hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const float* wp, int cin,
                         const View& mask, int epi, const View& dx, hipStream_t s) {
-  FwdArgs a{};
-  a.in = dy.p; a.in_stride = dy.stride; a.in_off = dy.off; a.IHt = 2 * h; a.IWt = 2 * w;
-  a.N = N; a.OH = h; a.OW = w; a.K = cout; a.NOUT = cin;
-  a.wp = wp; a.wp_z = 0;
-  a.bias = nullptr; a.epi = epi;
-  a.out = dx.p; a.out_stride = dx.stride; a.out_off = dx.off; a.out_layout = OUT_NHWC;
-  a.mask = mask.p; a.mask_stride = mask.stride; a.mask_off = mask.off;
+  FwdArgs a = fwd_args(dy, 2 * h, 2 * w, N, h, w, cout, cin, dx, OUT_NHWC);
+  a.wp = wp;
+  a.epi = epi;
+  set_mask(a, mask);
   return launch_fwd(G_DN2, a, s);
 }
 
@@ -415,9 +403,9 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
   const int N = p.N, nf = p.nf, C = p.C;
   auto H = [&](int l) { return p.H >> l; };
   auto Wd = [&](int l) { return p.W >> l; };
-  auto Wt = [&](int i) { return ws + p.packF[i]; };  // packed forward weights
   auto Bs = [&](int i) { return prm + p.P.L[i].woff + p.P.L[i].wcount; };
   auto V = [&](long off, int stride, int coff = 0) { return View{ws + off, stride, coff}; };
+  const View none{nullptr, 0, 0};
   // every 3x3 layer (enc_conv1..dec_conv1b): the fp32 kernel, the bf16x6 one (split fp32
   // operands on the bf16 matrix cores), or the bf16 one (bf16 operands, fp32 accumulation /
   // bias / activation / storage)
@@ -461,53 +449,42 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
   // (its full-resolution activation is read by nothing but that pool; the backward's pool
   // routing reads it in plans with a backward)
   const int pool_only = !p.with_bwd ? 1 : 0;
-  auto conv_forward = [&](const View& in, int Nn, int h, int w, int K, const float* wp,
-                          const float* b, int cout, int ksize, int act, const View& out,
-                          int layout, hipStream_t st, const View* pool = nullptr,
+  // Layer i (enc_conv1 .. nin_c) at its level, on the kernel of the pass's precision: channels,
+  // kernel size, bias and the weight image all come from the layer table and the plan's images
+  auto conv_forward = [&](int i, const View& in, int act, const View& out, int layout,
+                          hipStream_t st, const View* pool = nullptr,
                           bool* pooled = nullptr) -> hipError_t {
     if (pooled) *pooled = false;
-    const OpTimer timer(st, ksize == 3 ? "fwd3" : "fwd1",
-                        2.0 * Nn * h * w * K * cout * ksize * ksize, K, cout, h, w, Nn);
-    int i = ENC1;
-    while (i < NL && Wt(i) != wp) ++i;
-    if (x6 && i < NL && p.packX[i] >= 0) {
-      FwdArgs a{};
-      a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = h; a.IWt = w;
-      a.N = Nn; a.OH = h; a.OW = w; a.K = K; a.NOUT = cout;
-      // dec_conv1a reads [up1 | x | zero pad] (c1kp = c1k rounded to 4): taking the zero pad
-      // channel as a reduction channel (its packed weights are zero) keeps K % 4 == 0
-      if (i == D1A) a.K = p.c1kp;
+    const Layer& L = p.P.L[i];
+    const int l = layer_level(i), h = H(l), w = Wd(l);
+    const OpTimer timer(st, L.k == 3 ? "fwd3" : "fwd1",
+                        2.0 * N * h * w * L.cin * L.cout * L.k * L.k, L.cin, L.cout, h, w, N);
+    const bool on_x6 = x6 && p.packX[i] >= 0, on_bf16 = !on_x6 && bf16 && p.packBF[i] >= 0;
+    if (!on_x6 && !on_bf16)  // the fp32 kernel (dec_conv1a: its c1k real channels)
+      return dn::conv_forward(in, N, h, w, L.cin, ws + p.packF[i], Bs(i), L.cout, L.k, act, out,
+                              layout, st);
+    // dec_conv1a reads [up1 | x | zero pad] (c1kp = c1k rounded to 4): taking the zero pad
+    // channel as a reduction channel (its packed weights are zero) keeps K % 4 == 0 (pipelined)
+    FwdArgs a = fwd_args(in, N, h, w, i == D1A ? p.c1kp : L.cin, L.cout, out, layout);
+    a.bias = Bs(i); a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
+    if (on_x6) {
+      a.wp = ws + p.packX[i];
       a.x6_tail = x6_tail_f(i);  // a partial last K chunk packed over fewer stages
       if (a.x6_tail & X6_T1) a.in_t1 = x;  // the image channel straight from the network input
-      a.wp = ws + p.packX[i]; a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-      a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = layout;
-      if (pool && pool_fuse && act && layout == OUT_NHWC) {
-        a.pool_out = pool->p; a.pool_stride = pool->stride; a.pool_off = pool->off;
-        a.pool_only = pool_only;
-        if (pooled) *pooled = true;
-      }
-      return launch_fwd_x6(a, st);
+    } else {
+      a.wp = ws + p.packBF[i];
+      // the activations that only a bf16 3x3 conv reads (d_l a -> d_l b, d1a -> d1b) stored as
+      // bf16: the consumer rounds its staged operands to bf16 anyway, so the result is
+      // bit-identical and those tensors move half the bytes
+      a.out_bf16 = bf16_store_out(i);
+      a.in_bf16 = bf16_store_in(i);
     }
-    if (!bf16 || i == NL || p.packBF[i] < 0)
-      return dn::conv_forward(in, Nn, h, w, K, wp, b, cout, ksize, act, out, layout, st);
-    FwdArgs a{};
-    a.in = in.p; a.in_stride = in.stride; a.in_off = in.off; a.IHt = h; a.IWt = w;
-    a.N = Nn; a.OH = h; a.OW = w; a.K = K; a.NOUT = cout;
-    if (i == D1A) a.K = p.c1kp;  // the zero pad channel as in the x6 path: K % 4 == 0 (pipelined)
-    a.wp = ws + p.packBF[i]; a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-    a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = layout;
-    // the activations that only a bf16 3x3 conv reads (d_l a -> d_l b, d1a -> d1b) stored as
-    // bf16: the consumer rounds its staged operands to bf16 anyway, so the result is
-    // bit-identical and those tensors move half the bytes
-    a.out_bf16 = bf16_store_out(i);
-    a.in_bf16 = bf16_store_in(i);
-    // the encoder's pools fused as in the x6 path
-    if (pool && pool_fuse && act && ksize == 3 && layout == OUT_NHWC && !a.out_bf16) {
-      a.pool_out = pool->p; a.pool_stride = pool->stride; a.pool_off = pool->off;
-      a.pool_only = pool_only;
+    // the encoder's pools fused into the 3x3 epilogue
+    if (pool && pool_fuse && act && L.k == 3 && layout == OUT_NHWC && !a.out_bf16) {
+      set_pool(a, *pool, pool_only);
       if (pooled) *pooled = true;
     }
-    return launch_fwd_bf16(a, st, ksize);
+    return on_x6 ? launch_fwd_x6(a, st) : launch_fwd_bf16(a, st, L.k);
   };
 
   // the bf16x6 nin head (k_nin_head_x6), also at the pair pixels
@@ -521,28 +498,22 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
   // the input instead of a bf16 1x1 launch per output parity)
   auto deconv_x6_layer = [&](int i) { return (x6 || bf16) && p.packUX[i] >= 0; };
   // ConvTranspose2d(2,2): fp32 kernel, or the bf16 1x1 kernel per output parity
-  auto deconv_forward = [&](const View& xin, int Nn, int h, int w, int cin, const float* wp,
-                            const float* b, int cout, const View& out, hipStream_t st) -> hipError_t {
-    const OpTimer timer(st, "deconv", 2.0 * Nn * h * w * cin * cout * 4, cin, cout, h, w, Nn);
-    int i = ENC1;
-    while (i < NL && Wt(i) != wp) ++i;
-    if (i < NL && deconv_x6_layer(i)) {  // bf16x6 parity GEMMs on the layer's pre-split images
-      FwdArgs a{};
-      a.in = xin.p; a.in_stride = xin.stride; a.in_off = xin.off; a.IHt = h; a.IWt = w;
-      a.N = Nn; a.OH = h; a.OW = w; a.K = cin; a.NOUT = cout; a.bias = b;
-      a.out = out.p; a.out_stride = out.stride; a.out_off = out.off;
+  // (layer i's input lives one level below its output)
+  auto deconv_forward = [&](int i, const View& xin, const View& out, hipStream_t st) -> hipError_t {
+    const Layer& L = p.P.L[i];
+    const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
+    const OpTimer timer(st, "deconv", 2.0 * N * h * w * L.cin * L.cout * 4, L.cin, L.cout, h, w, N);
+    const bool on_x6 = deconv_x6_layer(i);
+    if (!on_x6 && !(bf16 && p.packBF[i] >= 0))
+      return dn::deconv_forward(xin, N, h, w, L.cin, ws + p.packF[i], Bs(i), L.cout, out, st);
+    FwdArgs a = fwd_args(xin, N, h, w, L.cin, L.cout, out, OUT_UP2);
+    a.bias = Bs(i); a.epi = EPI_BIAS;
+    if (on_x6) {  // bf16x6 parity GEMMs on the layer's pre-split images
       if (!deconv_x6_ok(a)) return hipErrorInvalidValue;
       // (the bf16 base: plain bf16 products, as its convs)
       return launch_deconv_x6(a, ws + p.packUX[i], st, bf16);
     }
-    if (!bf16 || i == NL || p.packBF[i] < 0)
-      return dn::deconv_forward(xin, Nn, h, w, cin, wp, b, cout, out, st);
-    FwdArgs a{};
-    a.in = xin.p; a.in_stride = xin.stride; a.in_off = xin.off; a.IHt = h; a.IWt = w;
-    a.N = Nn; a.OH = h; a.OW = w; a.K = cin; a.NOUT = cout;
-    a.wp = ws + p.packBF[i]; a.wp_z = bf16_pack_elems(cin, cout, 1);
-    a.bias = b; a.epi = EPI_BIAS;
-    a.out = out.p; a.out_stride = out.stride; a.out_off = out.off; a.out_layout = OUT_UP2;
+    a.wp = ws + p.packBF[i]; a.wp_z = bf16_pack_elems(L.cin, L.cout, 1);
     return launch_fwd_bf16(a, st, 1);
   };
 
@@ -621,8 +592,7 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
   {  // enc_conv1 + pool1 -> skip slice of c2
     const View pv = V(p.c[1], p.cs[1], 2 * nf);
     bool pooled = false;
-    DN_TRY(conv_forward(V(p.a0, nf), N, H(0), Wd(0), nf, Wt(ENC1), Bs(ENC1), nf, 3, 1,
-                        V(p.a1, nf), OUT_NHWC, s, &pv, &pooled));
+    DN_TRY(conv_forward(ENC1, V(p.a0, nf), 1, V(p.a1, nf), OUT_NHWC, s, &pv, &pooled));
     if (!pooled)
       DN_TIMED(s, "pool", 0, 0, 0, 0, 0, 0, launch_pool_fwd(ws + p.a1, N, H(0), Wd(0), nf, ws + p.c[1], p.cs[1], 2 * nf, s));
   }
@@ -632,69 +602,61 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
     const View in = (l == 4) ? V(p.c[4], p.cs[4], nf) : V(p.c[l], p.cs[l], 2 * nf);
     const View pv = l < 4 ? V(p.c[l + 1], p.cs[l + 1], (l + 1 == 4) ? nf : 2 * nf) : V(p.p5, nf, 0);
     bool pooled = false;
-    DN_TRY(conv_forward(in, N, H(l), Wd(l), nf, Wt(li), Bs(li), nf, 3, 1, V(p.a[l], nf), OUT_NHWC,
-                        s, &pv, &pooled));
+    DN_TRY(conv_forward(li, in, 1, V(p.a[l], nf), OUT_NHWC, s, &pv, &pooled));
     if (pooled) continue;
     DN_TIMED(s, "pool", 0, 0, 0, 0, 0, 0,
              launch_pool_fwd(ws + p.a[l], N, H(l), Wd(l), nf, pv.p, pv.stride, pv.off, s));
   }
-  DN_TRY(conv_forward(V(p.p5, nf), N, H(5), Wd(5), nf, Wt(ENC6), Bs(ENC6), nf, 3, 1, V(p.a6, nf),
-                      OUT_NHWC, s));
+  DN_TRY(conv_forward(ENC6, V(p.p5, nf), 1, V(p.a6, nf), OUT_NHWC, s));
   // decoder: up5 (a6 -> c5[0:nf]); dec5a/b at level 4
-  DN_TRY(deconv_forward(V(p.a6, nf), N, H(5), Wd(5), nf, Wt(UP5), Bs(UP5), nf, V(p.c[4], p.cs[4], 0),
-                        s));
+  DN_TRY(deconv_forward(UP5, V(p.a6, nf), V(p.c[4], p.cs[4], 0), s));
   const int up_idx[6] = {0, UP1, UP2, UP3, UP4, UP5};  // up_idx[k]: level k -> level k-1
   const int da_idx[5] = {0, D2A, D3A, D4A, D5A};
   for (int l = 4; l >= 1; --l) {
-    if (l < 4) {  // up_{l+1}: d_{l+1}b -> c_l[0:2nf]
-      DN_TRY(deconv_forward(V(p.db[l + 1], 2 * nf), N, H(l + 1), Wd(l + 1), 2 * nf,
-                            Wt(up_idx[l + 1]), Bs(up_idx[l + 1]), 2 * nf, V(p.c[l], p.cs[l], 0),
-                            s));
-    }
+    if (l < 4)  // up_{l+1}: d_{l+1}b -> c_l[0:2nf]
+      DN_TRY(deconv_forward(up_idx[l + 1], V(p.db[l + 1], 2 * nf), V(p.c[l], p.cs[l], 0), s));
     const int ia = da_idx[l], ib = da_idx[l] + 1;
-    DN_TRY(conv_forward(V(p.c[l], p.cs[l]), N, H(l), Wd(l), p.ck[l], Wt(ia), Bs(ia), 2 * nf, 3, 1,
-                        V(p.da[l], 2 * nf), OUT_NHWC, s));
-    DN_TRY(conv_forward(V(p.da[l], 2 * nf), N, H(l), Wd(l), 2 * nf, Wt(ib), Bs(ib), 2 * nf, 3, 1,
-                        V(p.db[l], 2 * nf), OUT_NHWC, s));
+    // (dec_conv{l}a reduces over the concat's ck[l] channels == its cin; cs[l] is the stride)
+    DN_TRY(conv_forward(ia, V(p.c[l], p.cs[l]), 1, V(p.da[l], 2 * nf), OUT_NHWC, s));
+    DN_TRY(conv_forward(ib, V(p.da[l], 2 * nf), 1, V(p.db[l], 2 * nf), OUT_NHWC, s));
   }
   // up1: d2b -> c1[0:2nf]
-  DN_TRY(deconv_forward(V(p.db[1], 2 * nf), N, H(1), Wd(1), 2 * nf, Wt(UP1), Bs(UP1), 2 * nf,
-                        V(p.c1, p.c1s, 0), s));
-  DN_TRY(conv_forward(V(p.c1, p.c1s), N, H(0), Wd(0), p.c1k, Wt(D1A), Bs(D1A), 96, 3, 1,
-                      V(p.d1a, 96), OUT_NHWC, s));
+  DN_TRY(deconv_forward(UP1, V(p.db[1], 2 * nf), V(p.c1, p.c1s, 0), s));
+  DN_TRY(conv_forward(D1A, V(p.c1, p.c1s), 1, V(p.d1a, 96), OUT_NHWC, s));
+  // the head kernels' common arguments (their input: the activated dec_conv1b output, 96 -> 96)
+  auto head_in = [&](long off, int h) {
+    return fwd_args(V(off, 96), N, h, Wd(0), 96, 96, none, OUT_NHWC);
+  };
+  auto head_args = [&]() {
+    HeadArgs h{};
+    h.ba = Bs(NINA); h.bb = Bs(NINB);
+    h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
+    h.y = y;
+    return h;
+  };
   if (bf16) {  // dec_conv1b, nin_a, nin_b on the bf16 kernel, then nin_c (96 -> out_nc, fp32)
-    DN_TRY(conv_forward(V(p.d1a, 96), N, H(0), Wd(0), 96, Wt(D1B), Bs(D1B), 96, 3, 1,
-                        V(p.d1b, 96), OUT_NHWC, s));
+    DN_TRY(conv_forward(D1B, V(p.d1a, 96), 1, V(p.d1b, 96), OUT_NHWC, s));
     if (bf16_head_x6) {
-      FwdArgs a{};
-      a.in = ws + p.d1b; a.in_stride = 96; a.in_off = 0; a.IHt = H(0); a.IWt = Wd(0);
-      a.N = N; a.OH = H(0); a.OW = Wd(0); a.K = 96; a.NOUT = 96;
-      HeadArgs h{};
-      h.wp = ws + p.packH;
-      h.ba = Bs(NINA); h.bb = Bs(NINB);
-      h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-      h.y = y;
+      FwdArgs a = head_in(p.d1b, H(0));
       a.in_bf16 = bf16_store_out(D1B);  // d1b stored as bf16 by dec_conv1b
+      HeadArgs h = head_args();
+      h.wp = ws + p.packH;
       DN_TIMED(s, "head", 2.0 * N * H(0) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0), Wd(0), N,
                launch_nin_head_x6(a, h, ws + p.packH, s, /*bf16=*/true));
       return DN_OK;
     }
-    DN_TRY(conv_forward(V(p.d1b, 96), N, H(0), Wd(0), 96, Wt(NINA), Bs(NINA), 96, 1, 1,
-                        V(p.na, 96), OUT_NHWC, s));
-    DN_TRY(conv_forward(V(p.na, 96), N, H(0), Wd(0), 96, Wt(NINB), Bs(NINB), 96, 1, 1,
-                        V(p.nb, 96), OUT_NHWC, s));
-    DN_TRY(dn::conv_forward(V(p.nb, 96), N, H(0), Wd(0), 96, Wt(NINC), Bs(NINC), p.OC, 1, 0,
-                            View{y, p.OC, 0}, OUT_NCHW, s));
+    DN_TRY(conv_forward(NINA, V(p.d1b, 96), 1, V(p.na, 96), OUT_NHWC, s));
+    DN_TRY(conv_forward(NINB, V(p.na, 96), 1, V(p.nb, 96), OUT_NHWC, s));
+    const Layer& Lc = p.P.L[NINC];
+    DN_TRY(dn::conv_forward(V(p.nb, 96), N, H(0), Wd(0), Lc.cin, ws + p.packF[NINC], Bs(NINC),
+                            Lc.cout, Lc.k, 0, View{y, p.OC, 0}, OUT_NCHW, s));
     return DN_OK;
   }
   // N2N no-grad pass (training_script.md:141-144 reads den at the pair pixels only): dec_conv1b
   // and the head on those pixels, through the [N, H/2, W, 96] pair image in d1b's storage
   if (sel) {
-    FwdArgs a{};
-    a.in = ws + p.d1a; a.in_stride = 96; a.in_off = 0; a.IHt = H(0); a.IWt = Wd(0);
-    a.N = N; a.OH = H(0); a.OW = Wd(0); a.K = 96; a.NOUT = 96;
+    FwdArgs a = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
     a.wp = ws + p.packX[D1B]; a.bias = Bs(D1B); a.epi = EPI_BIAS_ACT;
-    a.out = ws + p.d1b; a.out_stride = 96; a.out_off = 0; a.out_layout = OUT_NHWC;
     if (w6_sel) {  // the cells listed per tile orientation, then the Winograd pass over them
       unsigned* list = reinterpret_cast<unsigned*>(ws + p.w6s_list);
       int* cnt = reinterpret_cast<int*>(ws + p.w6s_cnt);
@@ -705,29 +667,18 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
       DN_TIMED(s, "fwd3sel", 2.0 * N * (H(0) / 2) * Wd(0) * 96 * 96 * 9, 96, 96, H(0) / 2, Wd(0), N,
                launch_fwd_x6_sel(a, s));
     }
-    FwdArgs ah{};
-    ah.in = ws + p.d1b; ah.in_stride = 96; ah.in_off = 0; ah.IHt = H(0) / 2; ah.IWt = Wd(0);
-    ah.N = N; ah.OH = H(0) / 2; ah.OW = Wd(0); ah.K = 96; ah.NOUT = 96;
-    HeadArgs h{};
-    h.ba = Bs(NINA); h.bb = Bs(NINB);
-    h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-    h.y = y;
+    const FwdArgs ah = head_in(p.d1b, H(0) / 2);
+    HeadArgs h = head_args();
     h.rd = sel_rd;
     DN_TIMED(s, "head", 2.0 * N * (H(0) / 2) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0) / 2,
              Wd(0), N, launch_nin_head_x6(ah, h, ws + p.packH, s));
     return DN_OK;
   }
   if (x6) {  // dec_conv1b on the bf16x6 kernel, then the fused nin_a -> nin_b -> nin_c head
-    DN_TRY(conv_forward(V(p.d1a, 96), N, H(0), Wd(0), 96, Wt(D1B), Bs(D1B), 96, 3, 1,
-                        V(p.d1b, 96), OUT_NHWC, s));
-    FwdArgs a{};
-    a.in = ws + p.d1b; a.in_stride = 96; a.in_off = 0; a.IHt = H(0); a.IWt = Wd(0);
-    a.N = N; a.OH = H(0); a.OW = Wd(0); a.K = 96; a.NOUT = 96;
-    HeadArgs h{};
+    DN_TRY(conv_forward(D1B, V(p.d1a, 96), 1, V(p.d1b, 96), OUT_NHWC, s));
+    const FwdArgs a = head_in(p.d1b, H(0));
+    HeadArgs h = head_args();
     h.wp = ws + p.packH;
-    h.ba = Bs(NINA); h.bb = Bs(NINB);
-    h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-    h.y = y;
     if (p.with_bwd) { h.na = ws + p.na; h.nb = ws + p.nb; }
     DN_TIMED(s, "head", 2.0 * N * H(0) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0), Wd(0), N,
              head_x6 ? launch_nin_head_x6(a, h, ws + p.packH, s) : launch_nin_head(a, h, s));
@@ -736,16 +687,10 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
   // dec_conv1b + nin_a + nin_b + nin_c in one kernel (arch_unet.py:251-257); the
   // intermediate activations are written only when a backward will read them
   {
-    FwdArgs a{};
-    a.in = ws + p.d1a; a.in_stride = 96; a.in_off = 0; a.IHt = H(0); a.IWt = Wd(0);
-    a.N = N; a.OH = H(0); a.OW = Wd(0); a.K = 96; a.NOUT = 96;
-    a.wp = Wt(D1B); a.wp_z = 0; a.bias = Bs(D1B); a.epi = EPI_BIAS_ACT;
-    a.out = ws + p.d1b; a.out_stride = 96; a.out_off = 0; a.out_layout = OUT_NHWC;
-    HeadArgs h{};
+    FwdArgs a = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
+    a.wp = ws + p.packF[D1B]; a.bias = Bs(D1B); a.epi = EPI_BIAS_ACT;
+    HeadArgs h = head_args();
     h.wp = ws + p.packH;
-    h.ba = Bs(NINA); h.bb = Bs(NINB);
-    h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-    h.y = y;
     if (p.with_bwd) { h.d1b = ws + p.d1b; h.na = ws + p.na; h.nb = ws + p.nb; }
     DN_TIMED(s, "fwd3+head", 2.0 * N * H(0) * Wd(0) * 96 * (9 * 96 + 2 * 96 + p.OC), 96, 96, H(0),
              Wd(0), N, launch_head(a, h, s));
@@ -810,6 +755,17 @@ SideStream* side_stream(hipStream_t s) {
   return &ss;
 }
 
+bool bwd_two_streams() {
+  static const bool on = !getenv("DN_BWD_STREAMS") || atoi(getenv("DN_BWD_STREAMS")) != 0;
+  return on;
+}
+
+hipError_t side_fork(SideStream* side, hipStream_t s) {
+  if (!side) return hipSuccess;
+  hipError_t e = hipEventRecord(side->fork, s);
+  return e != hipSuccess ? e : hipStreamWaitEvent(side->st, side->fork, 0);
+}
+
 long tail_begin(const Plan& p) { return p.P.L[D5A].woff; }
 
 dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float* dprm, float* dx,
@@ -821,7 +777,6 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   const int N = p.N, nf = p.nf, C = p.C;
   auto H = [&](int l) { return p.H >> l; };
   auto Wd = [&](int l) { return p.W >> l; };
-  auto Wt = [&](int i) { return ws + p.packB[i]; };  // packed data-gradient weights
   auto G = [&](int i) { return dprm + p.P.L[i].woff; };
   auto V = [&](long off, int stride, int coff = 0) { return View{ws + off, stride, coff}; };
   auto x6_tail_b = [&](int i) -> int {  // as x6_tail_f in the forward, for the data gradients
@@ -830,16 +785,18 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   };
   // bf16x6 data gradients of the 96-channel deconvs
   auto x6_dgrad_deconv = [&](int i) { return x6 && p.packUXB[i] >= 0; };
-  auto deconv_dgrad = [&](const View& dy, int Nn, int h, int w, int cout, int i, int cin,
-                          const View& mask, int epi, const View& dx, hipStream_t st) -> hipError_t {
-    const OpTimer timer(st, "deconv_dgrad", 2.0 * Nn * h * w * cin * cout * 4, cout, cin, h, w, Nn);
+  // deconv layer i: dy at the layer's output level -> dx one level below (* leaky'(mask))
+  auto deconv_dgrad = [&](int i, const View& dy, const View& mask, int epi, const View& dx,
+                          hipStream_t st) -> hipError_t {
+    const Layer& L = p.P.L[i];
+    const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
+    const OpTimer timer(st, "deconv_dgrad", 2.0 * N * h * w * L.cin * L.cout * 4, L.cout, L.cin, h,
+                        w, N);
     if (!x6_dgrad_deconv(i))
-      return dn::deconv_dgrad(dy, Nn, h, w, cout, Wt(i), cin, mask, epi, dx, st);
-    FwdArgs a{};
-    a.in = dy.p; a.in_stride = dy.stride; a.in_off = dy.off; a.IHt = 2 * h; a.IWt = 2 * w;
-    a.N = Nn; a.OH = h; a.OW = w; a.K = cout; a.NOUT = cin;
-    a.epi = epi; a.mask = mask.p; a.mask_stride = mask.stride; a.mask_off = mask.off;
-    a.out = dx.p; a.out_stride = dx.stride; a.out_off = dx.off;
+      return dn::deconv_dgrad(dy, N, h, w, L.cout, ws + p.packB[i], L.cin, mask, epi, dx, st);
+    FwdArgs a = fwd_args(dy, 2 * h, 2 * w, N, h, w, L.cout, L.cin, dx, OUT_NHWC);
+    a.epi = epi;
+    set_mask(a, mask);
     return launch_deconv_dgrad_x6(a, ws + p.packUXB[i], st);
   };
   // the head's data gradients in the bf16x6 arithmetic (k_head_bwd_x6)
@@ -880,15 +837,10 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   }
   RedBatch rb;  // every weight gradient's reduction, launched together at the end
   const float* Z = ws + p.zeros;
-  static const bool two_env = !getenv("DN_BWD_STREAMS") || atoi(getenv("DN_BWD_STREAMS")) != 0;
   // (profiling: one stream, so each launch's event pair brackets that kernel alone)
-  SideStream* side = two_env && !prof_on() ? side_stream(s) : nullptr;
+  SideStream* side = bwd_two_streams() && !prof_on() ? side_stream(s) : nullptr;
   hipStream_t s2 = side ? side->st : s;
-  auto fork = [&]() -> hipError_t {  // the side stream continues after main's work so far
-    if (!side) return hipSuccess;
-    hipError_t e = hipEventRecord(side->fork, s);
-    return e != hipSuccess ? e : hipStreamWaitEvent(side->st, side->fork, 0);
-  };
+  auto fork = [&] { return side_fork(side, s); };
   // the queued slab reductions on the reduction stream, behind the weight gradients queued on
   // the side stream so far (one stream: on s, in order)
   auto flush_side = [&]() -> hipError_t {
@@ -900,24 +852,21 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   };
   auto SL = [&](int i) { return ws + p.slab[i]; };
   // 3x3 data gradients: the fp32 kernel or the bf16x6 one
-  auto conv_dgrad = [&](const View& dz, int Nn, int h, int w, int cout, const float* wp, int nout,
-                        int ksize, int epi, const View& mask, const View& dx,
+  // layer i: dz (the layer's cout channels) -> dx, channels [0, dgrad_nout(p, i)) of its input
+  auto conv_dgrad = [&](int i, const View& dz, int epi, const View& mask, const View& dx,
                         hipStream_t st) -> hipError_t {
-    const OpTimer timer(st, ksize == 3 ? "dgrad3" : "dgrad1",
-                        2.0 * Nn * h * w * cout * nout * ksize * ksize, cout, nout, h, w, Nn);
-    int i = ENC1;
-    while (i < NL && Wt(i) != wp) ++i;
-    if (!x6 || i == NL || p.packXB[i] < 0 || ksize != 3)
-      return dn::conv_dgrad(dz, Nn, h, w, cout, wp, nout, ksize, epi, mask, dx, st);
-    FwdArgs a{};
-    a.in = dz.p; a.in_stride = dz.stride; a.in_off = dz.off; a.IHt = h; a.IWt = w;
-    a.N = Nn; a.OH = h; a.OW = w; a.K = cout; a.NOUT = nout;
+    const Layer& L = p.P.L[i];
+    const int l = layer_level(i), h = H(l), w = Wd(l), cout = L.cout, nout = dgrad_nout(p, i);
+    const OpTimer timer(st, L.k == 3 ? "dgrad3" : "dgrad1",
+                        2.0 * N * h * w * cout * nout * L.k * L.k, cout, nout, h, w, N);
+    if (!x6 || p.packXB[i] < 0)  // (packXB: the 3x3 layers)
+      return dn::conv_dgrad(dz, N, h, w, cout, ws + p.packB[i], nout, L.k, epi, mask, dx, st);
+    FwdArgs a = fwd_args(dz, N, h, w, cout, nout, dx, OUT_NHWC);
     a.zc = x6_dgrad_zc(nout);
     a.wp = ws + p.packXB[i];
     a.wp_z = a.zc ? x6_pack_elems(cout, nout, a.zc) / ((nout + a.zc - 1) / a.zc) : 0;
-    a.bias = nullptr; a.epi = epi;
-    a.out = dx.p; a.out_stride = dx.stride; a.out_off = dx.off; a.out_layout = OUT_NHWC;
-    a.mask = mask.p; a.mask_stride = mask.stride; a.mask_off = mask.off;
+    a.epi = epi;
+    set_mask(a, mask);
     a.x6_tail = x6_tail_b(i);
     return launch_fwd_x6(a, st);
   };
@@ -970,8 +919,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   DN_TRY(fork());
   DN_TRY(wgrad(W_C3, V(p.g_d1b, 96), V(p.d1a, 96), N, H(0), Wd(0), 96, 96, G(D1B), SL(D1B),
                p.splits[D1B], s2, x6w, Z, &rb));
-  DN_TRY(conv_dgrad(V(p.g_d1b, 96), N, H(0), Wd(0), 96, Wt(D1B), 96, 3, EPI_MASK,
-                    V(p.d1a, 96), V(p.g_d1a, 96), s));
+  DN_TRY(conv_dgrad(D1B, V(p.g_d1b, 96), EPI_MASK, V(p.d1a, 96), V(p.g_d1a, 96), s));
   // dec_conv1a weight gradient: the MFMA kernel over the up1 channels [0, 2nf) and the thin
   // kernel over the network-input channels [2nf, 2nf + C), each into its own slab rows and
   // reduced into its own columns of W[co][c1k][9]
@@ -1005,8 +953,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
                                  &rb));
   }
   // only the up1 part of the concat needs a gradient (pool0 is the network input)
-  DN_TRY(conv_dgrad(V(p.g_d1a, 96), N, H(0), Wd(0), 96, Wt(D1A), 2 * nf, 3, EPI_PLAIN, none,
-                    V(p.g_c1, 2 * nf), s));
+  DN_TRY(conv_dgrad(D1A, V(p.g_d1a, 96), EPI_PLAIN, none, V(p.g_c1, 2 * nf), s));
 
   // decoder levels 1..4: up_{l}(d_{l+1}b ...) ; here "dU" for level l-1's deconv
   const int up_idx[6] = {UP1, UP2, UP3, UP4, UP5, 0};
@@ -1018,21 +965,19 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     DN_TRY(fork());
     DN_TRY(wgrad(W_UP2, dU, V(p.db[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf, G(iu), SL(iu),
                  p.splits[iu], s2, x6, Z, &rb));
-    DN_TRY(deconv_dgrad(dU, N, H(l), Wd(l), 2 * nf, iu, 2 * nf, V(p.db[l], 2 * nf), EPI_MASK,
-                        V(p.g_db[l], 2 * nf), s));
+    DN_TRY(deconv_dgrad(iu, dU, V(p.db[l], 2 * nf), EPI_MASK, V(p.g_db[l], 2 * nf), s));
     const int ia = da_idx[l], ib = ia + 1;
     DN_TRY(fork());
     DN_TRY(wgrad(W_C3, V(p.g_db[l], 2 * nf), V(p.da[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf,
                  G(ib), SL(ib), p.splits[ib], s2, x6w, Z, &rb));
-    DN_TRY(conv_dgrad(V(p.g_db[l], 2 * nf), N, H(l), Wd(l), 2 * nf, Wt(ib), 2 * nf, 3,
-                      EPI_MASK, V(p.da[l], 2 * nf), V(p.g_da[l], 2 * nf), s));
+    DN_TRY(conv_dgrad(ib, V(p.g_db[l], 2 * nf), EPI_MASK, V(p.da[l], 2 * nf), V(p.g_da[l], 2 * nf),
+                      s));
     DN_TRY(fork());
     // channel count ck (the layer's cin, what G(ia) and the dgrad pack are sized for); cs is
     // only the pixel stride (larger under a DN_C1S_ALIGN override)
     DN_TRY(wgrad(W_C3, V(p.g_da[l], 2 * nf), V(p.c[l], p.cs[l]), N, H(l), Wd(l), 2 * nf, p.ck[l],
                  G(ia), SL(ia), p.splits[ia], s2, x6w, Z, &rb));
-    DN_TRY(conv_dgrad(V(p.g_da[l], 2 * nf), N, H(l), Wd(l), 2 * nf, Wt(ia), p.ck[l], 3,
-                      EPI_PLAIN, none, V(p.g_c[l], p.cs[l]), s));
+    DN_TRY(conv_dgrad(ia, V(p.g_da[l], 2 * nf), EPI_PLAIN, none, V(p.g_c[l], p.cs[l]), s));
     dU = V(p.g_c[l], p.cs[l], 0);  // [u_{l+1} grad | skip grad]
   }
   // the head's and the decoder's reductions on the side stream now, behind their weight
@@ -1047,14 +992,12 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   DN_TRY(fork());
   DN_TRY(wgrad(W_UP2, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), N, H(5), Wd(5), nf, nf, G(UP5), SL(UP5),
                p.splits[UP5], s2, false, Z, &rb));
-  DN_TRY(deconv_dgrad(V(p.g_c[4], p.cs[4], 0), N, H(5), Wd(5), nf, UP5, nf, V(p.a6, nf),
-                      EPI_MASK, V(p.g_a6, nf), s));
+  DN_TRY(deconv_dgrad(UP5, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), EPI_MASK, V(p.g_a6, nf), s));
   // enc_conv6 (input p5, level 5)
   DN_TRY(fork());
   DN_TRY(wgrad(W_C3, V(p.g_a6, nf), V(p.p5, nf), N, H(5), Wd(5), nf, nf, G(ENC6), SL(ENC6),
                p.splits[ENC6], s2, x6w, Z, &rb));
-  DN_TRY(conv_dgrad(V(p.g_a6, nf), N, H(5), Wd(5), nf, Wt(ENC6), nf, 3, EPI_PLAIN, none,
-                    V(p.g_p5, nf), s));
+  DN_TRY(conv_dgrad(ENC6, V(p.g_a6, nf), EPI_PLAIN, none, V(p.g_p5, nf), s));
   // pool5 backward -> g_a5 (level 4)
   DN_TIMED(s, "pool_bwd", 0, 0, 0, 0, 0, 0, launch_pool_bwd(ws + p.a[4], N, H(4), Wd(4), nf, ws + p.g_p5, nf, 0, 1, ws + p.g_a[4], s));
   // enc_conv5..2: input p_{l} = skip slice of c_l; gradient accumulates into g_c_l's skip slice
@@ -1064,8 +1007,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     DN_TRY(fork());
     DN_TRY(wgrad(W_C3, V(p.g_a[l], nf), V(p.c[l], p.cs[l], skip), N, H(l), Wd(l), nf, nf, G(li),
                  SL(li), p.splits[li], s2, x6w, Z, &rb));
-    DN_TRY(conv_dgrad(V(p.g_a[l], nf), N, H(l), Wd(l), nf, Wt(li), nf, 3, EPI_ACCUM, none,
-                      V(p.g_c[l], p.cs[l], skip), s));
+    DN_TRY(conv_dgrad(li, V(p.g_a[l], nf), EPI_ACCUM, none, V(p.g_c[l], p.cs[l], skip), s));
     // pool_l backward: d p_l (skip slice) -> gradient of the level l-1 activation
     if (l > 1) {
       DN_TIMED(s, "pool_bwd", 0, 0, 0, 0, 0, 0, launch_pool_bwd(ws + p.a[l - 1], N, H(l - 1), Wd(l - 1), nf, ws + p.g_c[l], p.cs[l],
@@ -1084,8 +1026,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   // enc_conv0's beside it on the side stream, which is still working through the encoder's
   // weight gradients (both streams end together instead of the side stream alone for ~0.5 ms,
   // profiles/r6_step_timeline.txt)
-  DN_TRY(conv_dgrad(V(p.g_a1, nf), N, H(0), Wd(0), nf, Wt(ENC1), nf, 3, EPI_MASK, V(p.a0, nf),
-                    V(p.g_a0, nf), s));
+  DN_TRY(conv_dgrad(ENC1, V(p.g_a1, nf), EPI_MASK, V(p.a0, nf), V(p.g_a0, nf), s));
   DN_TRY(fork());
   DN_TIMED(s2, "wgrad3_thin", 2.0 * N * H(0) * Wd(0) * nf * C * 9, C, nf, H(0), Wd(0), N,
            launch_enc0_wgrad(ws + p.g_a0, nf, ws + p.xin, N, C, H(0), Wd(0), SL(ENC0) + 64,

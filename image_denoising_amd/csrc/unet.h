@@ -101,6 +101,9 @@ struct SideStream {
   hipEvent_t rfork = nullptr, rjoin = nullptr;
 };
 SideStream* side_stream(hipStream_t s);
+bool bwd_two_streams();  // false under DN_BWD_STREAMS=0: the backward on one stream
+// the side stream continues after the work queued on s so far (side == nullptr: nothing to do)
+hipError_t side_fork(SideStream* side, hipStream_t s);
 
 long tail_begin(const Plan& p);
 // zc of the bf16x6 data gradient of a 3x3 layer producing nout channels (0: one block)

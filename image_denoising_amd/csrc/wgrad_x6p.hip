@@ -975,7 +975,9 @@ hipError_t launch_wgrad1p(const WgradArgs& a, int splits, hipStream_t s, bool up
     prof_kernel("k_wgrad1p<true>");
     hipLaunchKernelGGL(k_wgrad1p<true>, dim3(4 * splits), dim3(256), 0, s, a, npx);
   } else if (a.head_gnb > 0) {
+    // (hd_wc is read with 16-byte loads; a dy pixel holds head_gnb values)
     if (a.head_gnb > 4 || !a.hd_dy || !a.hd_wc || a.g_stride != 96 || a.g_off ||
+        (reinterpret_cast<uintptr_t>(a.hd_wc) & 15) || a.hd_dy_stride < a.head_gnb ||
         (a.hd_slab_c && a.head_gnb != 1))  // (the nin_c fold: one output only)
       return hipErrorInvalidValue;
     prof_kernel("k_wgrad1p<false,gnb>");
