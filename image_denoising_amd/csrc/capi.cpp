@@ -577,6 +577,8 @@ dn_status dn_conv2d_forward_x6(const float* x, int x_stride, int N, int H, int W
                          View{y, y_stride, 0}, OUT_NHWC);
     a.x6_tail = tail;
     a.wp = static_cast<const float*>(pack_ws); a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
+    // (dn_profile_ops: the record brackets the GEMM launch alone, so its label is the GEMM's)
+    const OpTimer timer(s, "fwd3", 2.0 * Cin * Cout * 9 * N * H * W, Cin, Cout, H, W, N);
     e = launch_fwd_x6(a, s);
   }
   return hip_status(e, "dn_conv2d_forward_x6");
@@ -606,6 +608,7 @@ dn_status dn_conv2d_backward_data_x6(const float* dz, int N, int H, int W, int C
     a.wp_z = zc ? x6_pack_elems(Cout, Cin, zc) / ((Cin + zc - 1) / zc) : 0;
     a.epi = mask ? EPI_MASK : (accumulate ? EPI_ACCUM : EPI_PLAIN);
     set_mask(a, View{const_cast<float*>(mask), mask_stride, 0});
+    const OpTimer timer(s, "dgrad3", 2.0 * Cout * Cin * 9 * N * H * W, Cout, Cin, H, W, N);
     e = launch_fwd_x6(a, s);
   }
   return hip_status(e, "dn_conv2d_backward_data_x6");
@@ -656,6 +659,8 @@ dn_status dn_conv2d_backward_weight_x6(const float* dz, const float* x, int x_st
   if (!dz || !x || !dwb || !slab) return fail(DN_ERR_ARG, "null argument");
   if (!wgrad_supported(W_C3, Cout, Cin)) return fail(DN_ERR_ARG, "unsupported Cout");
   const int sp = wgrad_splits(W_C3, N, H, W, Cin, Cout);
+  // (dn_profile_ops: wgrad() takes the "wgrad3" record itself; k_reduce_batch sets no label, so
+  // the record keeps the GEMM kernel's)
   return hip_status(wgrad(W_C3, View{const_cast<float*>(dz), Cout, 0},
                           View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cout, Cin, dwb,
                           static_cast<float*>(slab), sp, (hipStream_t)stream, true),

@@ -84,14 +84,17 @@ def test_subsample_matches_reference_fixture(golden, case):
     assert torch.equal(n2n.generate_subimages(img, m2), s2)
 
 
-def test_subsample_philox_stream_bitexact():
+# cell_base % 4 == 0 (with w % 4 == 0): k_subsample4, four cells of one Philox block per thread;
+# 777: the scalar k_subsample
+@pytest.mark.parametrize("cell_base", [777, 776, 0])
+def test_subsample_philox_stream_bitexact(cell_base):
     from image_denoising_amd import n2n
     from oracle import n2n_ref, philox
 
     img = torch.rand(3, 2, 64, 96, device=DEV)
     cells = 3 * 32 * 48
-    s1, s2, rd = n2n.n2n_subsample(img, None, seed=11, offset=5, cell_base=777)
-    ref_rd = philox.rd_idx(11, 5, cells, cell_base=777)
+    s1, s2, rd = n2n.n2n_subsample(img, None, seed=11, offset=5, cell_base=cell_base)
+    ref_rd = philox.rd_idx(11, 5, cells, cell_base=cell_base)
     assert np.array_equal(rd.cpu().numpy(), ref_rd)
     c1, c2 = n2n_ref.subimages_closed_form(img.cpu().numpy(), ref_rd)
     assert np.array_equal(s1.cpu().numpy(), c1) and np.array_equal(s2.cpu().numpy(), c2)
