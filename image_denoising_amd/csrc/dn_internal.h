@@ -160,6 +160,9 @@ struct WgradArgs {
   // (head_gnb) nin_c's weight gradient from the same nb / dy reads: one slab row per workgroup,
   // [oc][96] then the bias [oc] (k_wgrad_thin's layout), or null
   float* hd_slab_c; float* hd_dwc;  // (and its reduction's destination: nin_c's [W | b])
+  // k_wgrad3p / k_wgrad3q: every slab row segment of a workgroup starts and ends on 16 B, so the
+  // epilogue stages rows in LDS and writes float4 (set by launch_wgrad3p; 0: dword stores)
+  int slab_vec;
 };
 
 // strided NHWC view: element (pixel, c) at p[pixel * stride + off + c]

@@ -87,6 +87,50 @@ __device__ __forceinline__ int wp_idx(int r, int rw, int blk) {
 #define DN_WG_ABL_NOBAR 0
 #endif
 
+// ---- the staged slab epilogue (a.slab_vec) -------------------------------------------------
+// The accumulators of a lane are 4 output channels x 1 input channel x 9 taps: written straight
+// to the slab ([co][ci][t]) they are 4-byte stores 36 B apart, nine instructions per weight row.
+// After the stage loop's last barrier both stage buffers are free, so the workgroup's tile goes
+// through LDS in three passes (output fragment i of every wave: R = 16 rows per 48 output
+// channels) as rows [co][ci_local * 9 + t], the slab's own order for one co, and leaves as
+// float4 per lane, consecutive lanes on consecutive 16 B.  The values and their places are those
+// of the dword stores.
+//   Row pitch = row + 4 floats: one ds_write_b32 holds 16 input channels (9 dwords apart: 16
+//   distinct banks of 64, their pairwise distances the +-9k mod 64) x 4 rows; with the pitch
+//   4 mod 16 the rows sit 16 / 32 / 48 banks apart, distances that no two of the 16 have, so a
+//   write touches 64 distinct banks.  The pitch stays a multiple of 4 floats for the b128 reads.
+// launch_wgrad3p sets slab_vec when every row segment starts and ends on 16 B: cin_total,
+// ci_base, Cin, Cout (and the layer's) multiples of 4, the slab rows 16-B aligned.
+// The epilogue takes its lane index from mbcnt, not from threadIdx.x: a value derived after the
+// loop holds no register across the stage loop, which runs at the 256-register limit.
+__device__ __forceinline__ int slab_lane() {
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+template <int CIBK>
+struct SlabStage {
+  static constexpr int ROWQ = CIBK * 9 / 4;     // float4 of a full row (CIBK input channels)
+  static constexpr int PITCH = CIBK * 9 + 4;    // floats
+  static_assert(CIBK % 16 == 0 && PITCH % 16 == 4, "row pitch 4 mod 16 floats");
+};
+
+// pass i's rows out: row r of the stage = output channel (r / 16) * 48 + 16 i + r % 16 of the
+// launch, its first nq float4 valid; dst = the slab row segment of output channel 0
+template <int NTHR, int R, int CIBK>
+__device__ __forceinline__ void slab_rows_out(const float* st, float* dst, long co_pitch, int i,
+                                              int nq, int Cout, int tid) {
+  using S = SlabStage<CIBK>;
+#pragma unroll
+  for (int k = 0; k < (R * S::ROWQ + NTHR - 1) / NTHR; ++k) {
+    const int q = tid + k * NTHR;
+    const int row = q / S::ROWQ, c = q - row * S::ROWQ;
+    const int co = (row >> 4) * 48 + 16 * i + (row & 15);
+    if (row < R && c < nq && co < Cout)
+      *reinterpret_cast<f32x4*>(dst + co * co_pitch + 4 * c) =
+          *reinterpret_cast<const f32x4*>(st + row * S::PITCH + 4 * c);
+  }
+}
+
 // The next stage's G and X operands are loaded at the start of the stage and split into the other
 // buffer at its end (a whole stage of load latency for both)
 template <int SWL, int CO = 96>
@@ -346,6 +390,36 @@ __global__ __launch_bounds__(CO == 96 ? 256 : 192, 2) void k_wgrad3p(WgradArgs a
   float* slab = a.slab + (long)blockIdx.x * a.slab_stride;
   const int ci = ci0 + 16 * wn + li;
   const int cot = a.cout_total ? a.cout_total : a.Cout;
+  if (a.slab_vec) {  // (uniform; the loop ended on a barrier: both stage buffers are free)
+    using S = SlabStage<C::CIB>;
+    constexpr int R = 16 * (CO / 48);  // rows of a pass
+    static_assert((R * S::PITCH + CO) * 4 <= 2 * C::BUF * 2, "a pass and the bias row fit the stage buffers");
+    float* st = reinterpret_cast<float*>(lds);
+    const int nv = a.Cin - ci0 < C::CIB ? a.Cin - ci0 : C::CIB;  // valid input channels
+    float* dst = slab + ((long)a.co_base * a.cin_total + a.ci_base + ci0) * 9;
+    const int ln = slab_lane(), eli = ln & 15, elg = ln >> 4, etid = 64 * wave + ln;
+    if (do_bias && eli == 0) {
+#pragma unroll
+      for (int i = 0; i < MFW; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[R * S::PITCH + (3 * wm + i) * 16 + 4 * elg + r] = accb[i][0][r];
+    }
+#pragma unroll
+    for (int i = 0; i < MFW; ++i) {
+      if (i) __syncthreads();  // pass i - 1 read out
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          st[(16 * wm + 4 * elg + r) * S::PITCH + (16 * wn + eli) * 9 + t] = acc[t][i][0][r];
+      __syncthreads();
+      slab_rows_out<C::NTHR, R, C::CIB>(st, dst, (long)a.cin_total * 9, i, nv * 9 / 4, a.Cout, etid);
+      if (i == 0 && a.bias && blockIdx.y == 0 && 4 * etid < a.Cout)
+        *reinterpret_cast<f32x4*>(slab + (long)cot * a.cin_total * 9 + a.co_base + 4 * etid) =
+            *reinterpret_cast<const f32x4*>(st + R * S::PITCH + 4 * etid);
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < MFW; ++i)
 #pragma unroll
@@ -601,6 +675,37 @@ __global__ __launch_bounds__(256, 2) void k_wgrad3q(WgradArgs a) {
 
   float* slab = a.slab + (long)blockIdx.x * a.slab_stride;
   const int cot = a.cout_total ? a.cout_total : a.Cout;
+  if (a.slab_vec) {  // the staged epilogue of k_wgrad3p: pass i = output channels 16 i .. + 15
+    using S = SlabStage<C::CIB>;
+    static_assert((16 * S::PITCH + 48) * 4 <= 2 * C::BUF * 2, "a pass and the bias row fit the stage buffers");
+    float* st = reinterpret_cast<float*>(lds);
+    const int nv = a.Cin - ci0 < C::CIB ? a.Cin - ci0 : C::CIB;
+    float* dst = slab + ((long)a.co_base * a.cin_total + a.ci_base + ci0) * 9;
+    const int ln = slab_lane(), eli = ln & 15, elg = ln >> 4, etid = 64 * wave + ln;
+    if (do_bias && eli == 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[16 * S::PITCH + i * 16 + 4 * elg + r] = accb[i][r];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (i) __syncthreads();  // pass i - 1 read out
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k >= nk) continue;
+        const int p = 7 * wave + k, j = p / 9, t = p - 9 * j;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[(4 * elg + r) * S::PITCH + (16 * j + eli) * 9 + t] = acc[k][i][r];
+      }
+      __syncthreads();
+      slab_rows_out<C::NTHR, 16, C::CIB>(st, dst, (long)a.cin_total * 9, i, nv * 9 / 4, a.Cout, etid);
+      if (i == 0 && a.bias && blockIdx.y == 0 && 4 * etid < a.Cout)
+        *reinterpret_cast<f32x4*>(slab + (long)cot * a.cin_total * 9 + a.co_base + 4 * etid) =
+            *reinterpret_cast<const f32x4*>(st + 16 * S::PITCH + 4 * etid);
+    }
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
     if (k >= nk) continue;
@@ -642,28 +747,44 @@ bool wgrad3p_ok(const WgradArgs& a) {
 // the 3-wave k_wgrad3p<.., 48> measured faster (@64^2 0.120-0.127 vs 0.131-0.133 ms,
 // profiles/r5_wg_ab.log; @32^2 0.050 vs 0.065 ms in-step): with 7 fragments per wave the
 // shorter stages no longer hide the next stage's loads.
-hipError_t launch_wgrad3p(const WgradArgs& a, int splits, hipStream_t s, int nz) {
-  if (!wgrad3p_ok(a)) return hipErrorInvalidValue;
+// the staged float4 slab epilogue (SlabStage) needs every row segment of a workgroup, and the
+// bias row, to start and end on 16 B; dec_conv1a (Cin = 96 of cin_total = 97, or 99: rows of
+// 97 x 9 floats do not start on 16 B) and channel counts that are no multiple of 4 keep the dword
+// stores, and their launch-profiler label ends in " dword".  DN_WG_SLAB_SCALAR=1 forces the dword
+// stores: the two epilogues must agree bit for bit.  It is a test switch, read at every launch
+// (a getenv per weight-gradient launch, ~14 per step) so that one process can run both; like
+// any getenv it must not race with a setenv in another thread.
+static bool slab_vec_ok(const WgradArgs& a) {
+  const char* e = getenv("DN_WG_SLAB_SCALAR");
+  if (e && atoi(e) != 0) return false;
+  if ((a.cin_total | a.ci_base | a.Cin | a.Cout | a.cout_total | a.co_base) & 3) return false;
+  return (a.slab_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(a.slab) & 15) == 0;
+}
+
+hipError_t launch_wgrad3p(const WgradArgs& a0, int splits, hipStream_t s, int nz) {
+  if (!wgrad3p_ok(a0)) return hipErrorInvalidValue;
+  WgradArgs a = a0;
+  a.slab_vec = slab_vec_ok(a0) ? 1 : 0;
   if (!a.zc && a.Cout == 48) {
     const dim3 grid(splits, (a.Cin + 47) / 48, nz);
     if (a.KW >= 128) {
-      prof_kernel("k_wgrad3q<4>");
+      prof_kernel(a.slab_vec ? "k_wgrad3q<4>" : "k_wgrad3q<4> dword");
       hipLaunchKernelGGL(k_wgrad3q<4>, grid, dim3(256), 0, s, a);
     } else if (a.KW >= 16) {
-      prof_kernel("k_wgrad3p<4,48>");
+      prof_kernel(a.slab_vec ? "k_wgrad3p<4,48>" : "k_wgrad3p<4,48> dword");
       hipLaunchKernelGGL((k_wgrad3p<4, 48>), grid, dim3(192), 0, s, a);
     } else {
-      prof_kernel("k_wgrad3p<3,48>");
+      prof_kernel(a.slab_vec ? "k_wgrad3p<3,48>" : "k_wgrad3p<3,48> dword");
       hipLaunchKernelGGL((k_wgrad3p<3, 48>), grid, dim3(192), 0, s, a);
     }
     return hipGetLastError();
   }
   const dim3 grid(splits, (a.Cin + 31) / 32, nz), block(256);
   if (a.KW >= 16) {
-    prof_kernel("k_wgrad3p<4,96>");
+    prof_kernel(a.slab_vec ? "k_wgrad3p<4,96>" : "k_wgrad3p<4,96> dword");
     hipLaunchKernelGGL((k_wgrad3p<4>), grid, block, 0, s, a);
   } else {
-    prof_kernel("k_wgrad3p<3,96>");
+    prof_kernel(a.slab_vec ? "k_wgrad3p<3,96>" : "k_wgrad3p<3,96> dword");
     hipLaunchKernelGGL((k_wgrad3p<3>), grid, block, 0, s, a);
   }
   return hipGetLastError();
