@@ -25,26 +25,9 @@
 #include <type_traits>
 
 #include "conv_epi.h"
-#include "x6_core.h"
+#include "x6_tile.h"
 
 namespace dn {
-
-// profiling label of a template instantiation ("k_c3x6p<6,0>"; -1 = parameter absent)
-static std::string x6_kname(const char* k, int p0, int p1, int p2) {
-  std::string n = std::string(k) + "<" + std::to_string(p0);
-  for (int v : {p1, p2})
-    if (v >= 0) n += "," + std::to_string(v);
-  return n + ">";
-}
-// the same with one more template argument spelled out: x6_kmore(x6_kname(...), "false")
-static std::string x6_kmore(std::string n, const char* last) {
-  n.back() = ',';
-  return n.append(last).append(">");
-}
-
-#ifndef DN_X6_GDMA
-#define DN_X6_GDMA 0  // A/B switch: 1 = the 3x3 kernels' weight DMA as global_load_lds
-#endif
 
 template <int NT, int MT>
 struct XCfg {
@@ -75,15 +58,11 @@ __global__ __launch_bounds__(256, 2) void k_c3x6(FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
   const int li = lane & 15, lg = lane >> 4;
-  const int tiles_x = (a.OW + C::TW - 1) / C::TW;
-  int bxr, byr;  // XCD-aware tile order (conv_epi.h xcd_tile)
-  xcd_tile(bxr, byr);
-  const int ty0 = (bxr / tiles_x) * C::TH;
-  const int tx0 = (bxr % tiles_x) * C::TW;
-  const int n = byr;
-  const int iy0 = ty0 - 1, ix0 = tx0 - 1;
-  const float* inb = a.in + (long)n * a.IHt * a.IWt * a.in_stride + a.in_off;
-  const __bf16* wimg = reinterpret_cast<const __bf16*>(a.wp) + (long)blockIdx.z * a.wp_z;
+  const X6Tile tl = x6_tile<C, true>(a);
+  const int ty0 = tl.ty0, tx0 = tl.tx0, n = tl.n;
+  const __bf16* wimg = tl.wimg;
+  const int iy0 = tl.iy0, ix0 = tl.ix0;
+  const float* inb = tl.inb;
   const bool vec = ((a.in_stride | a.in_off) & 3) == 0;
   const int nch = (a.K + C::KC - 1) / C::KC;
   const int nst = 9 * nch;
@@ -94,6 +73,8 @@ __global__ __launch_bounds__(256, 2) void k_c3x6(FwdArgs a) {
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[m][q] = accl[m][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  // (pointer loads: this kernel serves unaligned views; its store_x stays a copy of x6_store_x
+  // on float4 registers -- on the shared helper the compiler schedules this kernel differently)
   float4 xr[C::XITEMS];
   auto load_x = [&](int k0) {
 #pragma unroll
@@ -145,15 +126,8 @@ __global__ __launch_bounds__(256, 2) void k_c3x6(FwdArgs a) {
       const_cast<__bf16*>(wimg), (short)0, nst * C::WSTP * 2, 0x00020000);
   auto load_w = [&](int st, __bf16* dst) {  // stage st = chunk * 9 + tap, whole KiB pieces
 #pragma unroll
-    for (int p = wave; p < C::WST / 512; p += 4) {
-#if DN_X6_GDMA
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(wimg + (long)st * C::WSTP + p * 512 + lane * 8),
-          (__attribute__((address_space(3))) void*)(dst + p * 512), 16, 0, 0);
-#else
+    for (int p = wave; p < C::WST / 512; p += 4)
       buf_lds16(wrs, dst + p * 512, (st * C::WSTP + p * 512 + lane * 8) * 2);
-#endif
-    }
   };
 
   load_w(0, lw0);
@@ -202,12 +176,12 @@ __global__ __launch_bounds__(256, 2) void k_c3x6(FwdArgs a) {
 // chunk's x tile, which is loaded into registers when a chunk starts and split into the
 // three LDS planes when it ends.  Requires float4-aligned input views with K % 4 == 0.
 // ------------------------------------------------------------------------------------
-template <int NT, int WV = 8>
+template <int NT>
 struct PCfg {
-  // WV = 8: two waves per SIMD, MT = 2 rows each.  WV = 4 (one wave per SIMD, 4 rows, 392-462
-  // registers with the accumulators in AGPRs, no spills) measured 8-15 % slower on the 96-channel
-  // shapes (profiles/r3_ab_w4_not_kept.log): not launched
-  static constexpr int WAVES = WV, MT = 16 / WV, S = 4;
+  // 8 waves: two per SIMD, MT = 2 rows each.  4 waves (one per SIMD, 4 rows, 392-462 registers
+  // with the accumulators in AGPRs, no spills) measured 8-15 % slower on the 96-channel shapes
+  // (profiles/r3_ab_w4_not_kept.log)
+  static constexpr int WAVES = 8, MT = 2, S = 4;
   static constexpr int TW = 16, TH = WAVES * MT, IH = TH + 2, IW = TW + 2, KC = 32, NP = 16 * NT;
   static constexpr int XPIX = IH * IW;
   static constexpr int XPL = XPIX * KC;
@@ -224,48 +198,6 @@ struct PCfg {
   static_assert(LBYTES <= 163840, "one workgroup per CU");
 };
 
-#define X6_WAITCNT_VM(n) \
-  __builtin_amdgcn_s_waitcnt(((n) & 0xF) | (((n) >> 4) << 14) | (0x7 << 4) | (0xF << 8))
-// the same with lgkmcnt(0): at a stage's end every LDS read has been consumed, so the wait is
-// free, and it clears the compiler's view of the stage's weight DMAs as pending LGKM events --
-// otherwise the next stage's first MFMA waits lgkmcnt(0) for all of its operand reads instead
-// of the counted lgkmcnt(N) for the first few (the waitcnt pass treats global_load_lds as an
-// out-of-order LGKM event)
-#define X6_WAITCNT_VM_LGKM0(n) \
-  __builtin_amdgcn_s_waitcnt(((n) & 0xF) | (((n) >> 4) << 14) | (0x7 << 4))
-
-__device__ __forceinline__ void x6_barrier() {
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);  // no compiler motion of LDS accesses across it
-  __builtin_amdgcn_s_barrier();
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
-
-// SEL: a.sel_rd's N2N pair pixels only (launch_fwd_x6_sel): the 16 selected pixels (2 per cell)
-// of one row of 2x2 cells form ONE M fragment (the lane of fragment row 2j + s reads its A
-// operand at the pixel pair[rd][s] of cell j): half the MFMAs, the same staging, per-pixel
-// arithmetic unchanged (bit-identical outputs).  Wave w computes cell rows 2(w&3), 2(w&3)+1 of
-// the tile for output channels [NT/2 * 16 (w>>2), +NT/2 * 16): two M fragments x NT/2 B
-// fragments per stage (6 + 9 operand reads) instead of one cell row x NT (3 + 18) -- the B
-// reads had made the LDS array, not the matrix core, the limit.  The epilogue writes row
-// ty0/2 + 2(w&3) + m of the [OH/2][OW] pair image, channels of the wave's half.
-#ifndef DN_X6P_STAGED
-#define DN_X6P_STAGED 1  // A/B switch: the pipelined first fragment group of a k_c3x6p stage
-#endif
-#ifndef DN_X6P_LOOK
-#define DN_X6P_LOOK 2  // B fragment groups read ahead of their MFMAs in k_c3x6p
-#endif
-// A/B switches of the k_c3x6p stage schedule (full chunks): DMAI = the next weight stage's DMA
-// pieces issued between the first fragment groups instead of after the last MFMA; PIN = each
-// group's round-to-nearest hi adds pinned behind its MFMAs instead of sunk to the stage end
-#ifndef DN_X6P_DMAI
-#define DN_X6P_DMAI 1
-#endif
-#ifndef DN_X6P_PIN
-#define DN_X6P_PIN 1
-#endif
-#ifndef DN_X6P_ABL_NODMA
-#define DN_X6P_ABL_NODMA 0  // diagnostic ablation: no weight DMA in the stage loop (wrong results)
-#endif
 // DN_X6_STAMPS=1 (diagnostic builds only): s_memtime stamps of waves 0 and 4 (one per SIMD pair
 // half) of the first 64 tiles of image 0 -- kernel start, per stage after its opening barrier /
 // after its last MFMA / before its closing barrier, end of the main loop, end of the epilogue --
@@ -274,8 +206,6 @@ __device__ __forceinline__ void x6_barrier() {
 #ifndef DN_X6_STAMPS
 #define DN_X6_STAMPS 0
 #endif
-// A/B switch: static priority 1 for waves 4-7 (the second-dispatched half, the arbitration
-// loser of every stage) before the main loop (MI355X_MICROARCH.md, two waves per SIMD, item 4)
 #if DN_X6_STAMPS
 constexpr int X6_STAMP_SLOTS = 128;
 __device__ unsigned long long g_x6_stamps[64 * 2 * X6_STAMP_SLOTS];
@@ -293,10 +223,18 @@ __device__ unsigned long long g_x6_stamps[64 * 2 * X6_STAMP_SLOTS];
   } while (0)
 #endif
 
-template <int NT, int TAIL, bool SEL = false, int WV = 8>
-__global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
-  using C = PCfg<NT, WV>;
-  static_assert(!SEL || (TAIL == 0 && NT % 2 == 0 && C::MT == 2 && C::WAVES == 8),
+// SEL: a.sel_rd's N2N pair pixels only (launch_fwd_x6_sel): the 16 selected pixels (2 per cell)
+// of one row of 2x2 cells form ONE M fragment (the lane of fragment row 2j + s reads its A
+// operand at the pixel pair[rd][s] of cell j): half the MFMAs, the same staging, per-pixel
+// arithmetic unchanged (bit-identical outputs).  Wave w computes cell rows 2(w&3), 2(w&3)+1 of
+// the tile for output channels [NT/2 * 16 (w>>2), +NT/2 * 16): two M fragments x NT/2 B
+// fragments per stage (6 + 9 operand reads) instead of one cell row x NT (3 + 18) -- the B
+// reads had made the LDS array, not the matrix core, the limit.  The epilogue writes row
+// ty0/2 + 2(w&3) + m of the [OH/2][OW] pair image, channels of the wave's half.
+template <int NT, int TAIL, bool SEL = false>
+__global__ __launch_bounds__(64 * PCfg<NT>::WAVES, 1) void k_c3x6p(FwdArgs a) {
+  using C = PCfg<NT>;
+  static_assert(!SEL || (TAIL == 0 && NT % 2 == 0),
                 "selected pixels: full 32-channel chunks, 8 waves of two cell rows x NT/2");
   constexpr int MTC = C::MT;               // M fragments computed per wave
   constexpr int NTW = SEL ? NT / 2 : NT;   // B fragments per wave
@@ -307,15 +245,9 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
   const int li = lane & 15, lg = lane >> 4;
-  const int tiles_x = (a.OW + C::TW - 1) / C::TW;
-  int bxr, byr;  // XCD-aware tile order (conv_epi.h xcd_tile)
-  xcd_tile(bxr, byr);
-  const int ty0 = (bxr / tiles_x) * C::TH;
-  const int tx0 = (bxr % tiles_x) * C::TW;
-  const int n = byr;
-  const int iy0 = ty0 - 1, ix0 = tx0 - 1;
-  const float* inb = a.in + (long)n * a.IHt * a.IWt * a.in_stride + a.in_off;
-  const __bf16* wimg = reinterpret_cast<const __bf16*>(a.wp) + (long)blockIdx.z * a.wp_z;
+  const X6Tile tl = x6_tile<C, true>(a);
+  const int ty0 = tl.ty0, tx0 = tl.tx0, n = tl.n;
+  const __bf16* wimg = tl.wimg;
   const int nch = (a.K + C::KC - 1) / C::KC;
   // last chunk packed by x6_tail_mode: 2 im2col stages (mode 1) or 5 tap-pair stages (mode 2)
   constexpr int tail = TAIL;
@@ -351,45 +283,10 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
   // The resource covers only this tile's input rows [ry0, ry1) (based at row ry0), so its
   // 32-bit byte extent and offsets stay below 2^31 for any image height (launch_fwd_x6 checks
   // IH * IWt * in_stride * 4 < 2^31); 0x7fffffff is then always out of range.
-  const int ry0 = iy0 > 0 ? iy0 : 0, ry1 = iy0 + C::IH < a.IHt ? iy0 + C::IH : a.IHt;
-  const long row_floats = (long)a.IWt * a.in_stride;
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(inb + ry0 * row_floats), (short)0,
-      (int)((ry1 - ry0) * row_floats * 4), 0x00020000);
+  const X6XRows xrows = x6_x_rows<C>(a, tl);
   f32x4 xr[C::XITEMS];
-  auto load_x = [&](int k0) {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-      const int iy = pix / C::IW, ix = pix - iy * C::IW;
-      const int gy = iy0 + iy, gx = ix0 + ix, k = k0 + 4 * q;
-      const bool ok = e < C::XQ && gy >= 0 && gy < a.IHt && gx >= 0 && gx < a.IWt && k < a.K;
-      const int off = ok ? (((gy - ry0) * a.IWt + gx) * a.in_stride + k) * 4 : 0x7fffffff;
-      xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0));
-    }
-  };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      if (e < C::XQ) {
-        const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-        const float f[4] = {xr[it][0], xr[it][1], xr[it][2], xr[it][3]};
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          __bf16 hj, mj, lj;
-          split3(f[j], hj, mj, lj);
-          h[j] = hj; m[j] = mj; l[j] = lj;
-        }
-        const int off = pix * C::KC + x6_swz(pix, q >> 1) * 8 + (q & 1) * 4;
-        *reinterpret_cast<bf16x4*>(lx + off) = h;
-        *reinterpret_cast<bf16x4*>(lx + C::XPL + off) = m;
-        *reinterpret_cast<bf16x4*>(lx + 2 * C::XPL + off) = l;
-      }
-    }
-  };
+  auto load_x = [&](int k0) { x6_load_x<C>(a, tl, xrows, tid, k0, xr); };
+  auto store_x = [&]() { x6_store_x<C>(lx, tid, xr); };
   // weights of stage `src_st` into ring slot `slot`: PPW DMAs of 1 KiB per wave, as buffer loads
   // to LDS (MUBUF): the FLAT-encoded global_load_lds counts as a pending FLAT access, which makes
   // the compiler's waitcnt pass treat every later LDS-read wait as out of order (lgkmcnt(0)
@@ -397,7 +294,6 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<__bf16*>(wimg), (short)0, nst * C::WSTP * 2, 0x00020000);
   auto load_w_piece = [&](int src_st, int slot, int j) {
-    if (DN_X6P_ABL_NODMA) return;  // diagnostic ablation only: stale weights
     unsigned char* dst = reinterpret_cast<unsigned char*>(ring + slot * C::WSTP);
     const int piece = wave * C::PPW + j;
     buf_lds16(wrs, dst + piece * 1024, src_st * C::WSTP * 2 + piece * 1024 + lane * 16);
@@ -407,14 +303,7 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
 #pragma unroll
     for (int j = 0; j < C::PPW; ++j) {
       const int piece = wave * C::PPW + j;
-#if DN_X6_GDMA
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(wimg) +
-                                                          (long)src_st * C::WSTP * 2 + piece * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(dst + piece * 1024), 16, 0, 0);
-#else
       buf_lds16(wrs, dst + piece * 1024, src_st * C::WSTP * 2 + piece * 1024 + lane * 16);
-#endif
     }
   };
 
@@ -447,13 +336,15 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
     // MODE 3: the last chunk's mode decided at run time (tail instantiations: one A-read path
     // with branches keeps them at <= 256 VGPRs; two peeled paths would spill)
     const int mode = MODE == 3 ? ((tail && c + 1 == nch) ? tail : 0) : MODE;
-    constexpr int QG = x6_qgc(MTC, NTW), NG = NTW / QG, LOOK = NG < DN_X6P_LOOK ? NG : DN_X6P_LOOK;
+    constexpr int QG = x6_qgc(MTC, NTW), NG = NTW / QG, LOOK = NG < 2 ? NG : 2;
     // STAGED (full chunks, carried form): the stage's first fragment group is issued as a
     // read/compute pipeline -- A plane p and B plane p of group 0 requested one step before the
     // MFMAs that use them -- so the first MFMA waits for 3 reads, not for all 6 A + 6 B reads
     // of a stage that all 8 waves issue together after the barrier (384 LDS cycles); the MFMA
     // order per accumulator is that of x6_group_c (results unchanged bit for bit)
-    constexpr bool STAGED = MODE == 0 && QG == 1 && NG >= 3 && DN_X6P_STAGED;
+    constexpr bool STAGED = MODE == 0 && QG == 1 && NG >= 3;
+    // (k_c3x6h reads its A operand the same three ways; as one shared helper the tail and
+    // NT = 2 instantiations of both kernels compiled to different code, so each keeps its copy)
     if constexpr (STAGED) {
     } else if (mode == 1) {
       // im2col stage t: lane group lg holds k = 8lg..8lg+7 = channels 0..3 of taps
@@ -534,15 +425,15 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
     // compiler had sunk all of them to the stage end, behind the last MFMA, keeping 12 hi
     // temporaries live and adding 48 dependent adds to the tail the partner wave waits on
     auto pin_group = [&](int g) {
-      if constexpr (DN_X6P_PIN) {
 #pragma unroll
-        for (int m = 0; m < MTC; ++m)
+      for (int m = 0; m < MTC; ++m)
 #pragma unroll
-          for (int q = g * QG; q < (g + 1) * QG; ++q) asm volatile("" : "+v"(acc[m][q]));
-      }
+        for (int q = g * QG; q < (g + 1) * QG; ++q) asm volatile("" : "+v"(acc[m][q]));
     };
+    // STAGED also issues the next weight stage's DMA pieces between its first fragment groups
+    // (one per group) instead of after the last MFMA
     if constexpr (STAGED) {
-      static_assert(!DN_X6P_DMAI || C::PPW <= NG, "one DMA piece per early fragment group");
+      static_assert(C::PPW <= NG, "one DMA piece per early fragment group");
       const int ky = t / 3, kx = t - 3 * ky;
       auto read_a = [&](int p) {
 #pragma unroll
@@ -587,14 +478,14 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
         for (int r = 0; r < 4; ++r) acc[m][0][r] = acc[m][0][r] + hi[m][r];
       pin_group(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (DN_X6P_DMAI) load_w_piece(wsrc, wslot, 0);
+      load_w_piece(wsrc, wslot, 0);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int g = 1; g < NG; ++g) {
         x6_group_c<MTC, NTW, QG>(acc, accl, av, bv, g * QG);
         pin_group(g);
         __builtin_amdgcn_sched_barrier(0);
-        if (DN_X6P_DMAI && g < C::PPW) load_w_piece(wsrc, wslot, g);
+        if (g < C::PPW) load_w_piece(wsrc, wslot, g);
         if (g + 2 < NG) read_b(g + 2);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -617,15 +508,14 @@ __global__ __launch_bounds__(64 * WV, 1) void k_c3x6p(FwdArgs a) {
       store_x();
       load_x((c + 2 < nch ? c + 2 : nch - 1) * C::KC);  // uniform count: re-load at the end
     }
-    constexpr bool DMAI = STAGED && DN_X6P_DMAI;
-    if (!DMAI) load_w(wsrc, wslot);
+    if (!STAGED) load_w(wsrc, wslot);
     // own DMAs of stage st+1 landed: issued after them are those of stages st+2, st+S-1 and the
     // next-but-one chunk's x loads when issued in this stage (xstep) or the previous one (a
     // chunk's first stage) -- the x loads are not waited for here
     // (stages 0 and 1: the prologue's chunk-1 x loads are younger than their DMAs)
-    // DMAI: a stage's weight DMAs precede its x loads, so the x loads of stage st-2 (a chunk's
+    // STAGED: a stage's weight DMAs precede its x loads, so the x loads of stage st-2 (a chunk's
     // second stage, t == 1) are younger than stage st+1's DMAs too
-    if (xstep || (t == 0 && c > 0) || (DMAI && t == 1 && c > 0) || (c == 0 && t < 2))
+    if (xstep || (t == 0 && c > 0) || (STAGED && t == 1 && c > 0) || (c == 0 && t < 2))
       X6_WAITCNT_VM_LGKM0(C::PPW * (C::S - 2) + C::XITEMS);
     else
       X6_WAITCNT_VM_LGKM0(C::PPW * (C::S - 2));
@@ -717,15 +607,9 @@ __global__ __launch_bounds__(512, 1) void k_c3x6s(FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int tiles_x = (a.OW + C::TW - 1) / C::TW;
-  int bxr, byr;  // XCD-aware tile order (conv_epi.h xcd_tile)
-  xcd_tile(bxr, byr);
-  const int ty0 = (bxr / tiles_x) * C::TH;
-  const int tx0 = (bxr % tiles_x) * C::TW;
-  const int n = byr;
-  const int iy0 = ty0 - 1, ix0 = tx0 - 1;
-  const float* inb = a.in + (long)n * a.IHt * a.IWt * a.in_stride + a.in_off;
-  const __bf16* wimg = reinterpret_cast<const __bf16*>(a.wp);
+  const X6Tile tl = x6_tile<C, false>(a);
+  const int ty0 = tl.ty0, tx0 = tl.tx0, n = tl.n;
+  const __bf16* wimg = tl.wimg;
   const int nch = a.K / C::KC;
   const int nst = 9 * nch;
 
@@ -749,45 +633,10 @@ __global__ __launch_bounds__(512, 1) void k_c3x6s(FwdArgs a) {
   }
 
   // x tile rows through a 32-bit buffer resource (see k_c3x6p)
-  const int ry0 = iy0 > 0 ? iy0 : 0, ry1 = iy0 + C::IH < a.IHt ? iy0 + C::IH : a.IHt;
-  const long row_floats = (long)a.IWt * a.in_stride;
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(inb + ry0 * row_floats), (short)0,
-      (int)((ry1 - ry0) * row_floats * 4), 0x00020000);
+  const X6XRows xrows = x6_x_rows<C>(a, tl);
   f32x4 xr[C::XITEMS];
-  auto load_x = [&](int k0) {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-      const int iy = pix / C::IW, ix = pix - iy * C::IW;
-      const int gy = iy0 + iy, gx = ix0 + ix, k = k0 + 4 * q;
-      const bool ok = e < C::XQ && gy >= 0 && gy < a.IHt && gx >= 0 && gx < a.IWt && k < a.K;
-      const int off = ok ? (((gy - ry0) * a.IWt + gx) * a.in_stride + k) * 4 : 0x7fffffff;
-      xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0));
-    }
-  };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      if (e < C::XQ) {
-        const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-        const float f[4] = {xr[it][0], xr[it][1], xr[it][2], xr[it][3]};
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          __bf16 hj, mj, lj;
-          split3(f[j], hj, mj, lj);
-          h[j] = hj; m[j] = mj; l[j] = lj;
-        }
-        const int off = pix * C::KC + x6_swz(pix, q >> 1) * 8 + (q & 1) * 4;
-        *reinterpret_cast<bf16x4*>(lx + off) = h;
-        *reinterpret_cast<bf16x4*>(lx + C::XPL + off) = m;
-        *reinterpret_cast<bf16x4*>(lx + 2 * C::XPL + off) = l;
-      }
-    }
-  };
+  auto load_x = [&](int k0) { x6_load_x<C>(a, tl, xrows, tid, k0, xr); };
+  auto store_x = [&]() { x6_store_x<C>(lx, tid, xr); };
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<__bf16*>(wimg), (short)0, nst * C::WSTP * 2, 0x00020000);
   // piece j of stage src_st into slot `slot`: pieces w, w + 8, w + 16 (waves 2..7 repeat w + 8:
@@ -936,15 +785,6 @@ struct HCfg {
   static_assert(2 * LBYTES <= 163840, "two workgroups per CU");
 };
 
-#ifndef DN_X6H_LOOK
-#define DN_X6H_LOOK 2  // B fragment groups read ahead of their MFMAs in k_c3x6h
-#endif
-#ifndef DN_X6H_CARRY4
-#define DN_X6H_CARRY4 1  // A/B switch: 1 = MT = 4 with NT <= 3 carries the corrections too (96 acc VGPRs)
-#endif
-#ifndef DN_X6H_PIN
-#define DN_X6H_PIN 0  // A/B switch: 1 = MT = 2's hi adds pinned per group (100->96 @256^2: 1-2 % slower)
-#endif
 // S_ = 3 (small grids, MT = 1): a 3-slot weight ring, stage st + 2 requested at the start of st,
 // so a stage waits on neither the L2 latency of its weights nor that of the next stage's
 template <int NT, int TAIL, int MT_ = 2, int S_ = 2>
@@ -958,15 +798,9 @@ __global__ __launch_bounds__(256, 2) void k_c3x6h(FwdArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (SGPR)
   const int li = lane & 15, lg = lane >> 4;
-  const int tiles_x = (a.OW + C::TW - 1) / C::TW;
-  int bxr, byr;  // XCD-aware tile order (conv_epi.h xcd_tile)
-  xcd_tile(bxr, byr);
-  const int ty0 = (bxr / tiles_x) * C::TH;
-  const int tx0 = (bxr % tiles_x) * C::TW;
-  const int n = byr;
-  const int iy0 = ty0 - 1, ix0 = tx0 - 1;
-  const float* inb = a.in + (long)n * a.IHt * a.IWt * a.in_stride + a.in_off;
-  const __bf16* wimg = reinterpret_cast<const __bf16*>(a.wp) + (long)blockIdx.z * a.wp_z;
+  const X6Tile tl = x6_tile<C, true>(a);
+  const int ty0 = tl.ty0, tx0 = tl.tx0, n = tl.n;
+  const __bf16* wimg = tl.wimg;
   const int nch = (a.K + C::KC - 1) / C::KC;
   constexpr int tail = TAIL;
   constexpr int tail_st = tail == 1 ? 2 : 5;
@@ -979,45 +813,10 @@ __global__ __launch_bounds__(256, 2) void k_c3x6h(FwdArgs a) {
     for (int q = 0; q < NT; ++q) acc[m][q] = accl[m][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // input rows of this tile through a 32-bit buffer resource (see k_c3x6p)
-  const int ry0 = iy0 > 0 ? iy0 : 0, ry1 = iy0 + C::IH < a.IHt ? iy0 + C::IH : a.IHt;
-  const long row_floats = (long)a.IWt * a.in_stride;
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(inb + ry0 * row_floats), (short)0, (int)((ry1 - ry0) * row_floats * 4),
-      0x00020000);
+  const X6XRows xrows = x6_x_rows<C>(a, tl);
   f32x4 xr[C::XITEMS];
-  auto load_x = [&](int k0) {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-      const int iy = pix / C::IW, ix = pix - iy * C::IW;
-      const int gy = iy0 + iy, gx = ix0 + ix, k = k0 + 4 * q;
-      const bool ok = e < C::XQ && gy >= 0 && gy < a.IHt && gx >= 0 && gx < a.IWt && k < a.K;
-      const int off = ok ? (((gy - ry0) * a.IWt + gx) * a.in_stride + k) * 4 : 0x7fffffff;
-      xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0));
-    }
-  };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int it = 0; it < C::XITEMS; ++it) {
-      const int e = tid + it * C::WAVES * 64;
-      if (e < C::XQ) {
-        const int q = e % (C::KC / 4), pix = e / (C::KC / 4);
-        const float f[4] = {xr[it][0], xr[it][1], xr[it][2], xr[it][3]};
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          __bf16 hj, mj, lj;
-          split3(f[j], hj, mj, lj);
-          h[j] = hj; m[j] = mj; l[j] = lj;
-        }
-        const int off = pix * C::KC + x6_swz(pix, q >> 1) * 8 + (q & 1) * 4;
-        *reinterpret_cast<bf16x4*>(lx + off) = h;
-        *reinterpret_cast<bf16x4*>(lx + C::XPL + off) = m;
-        *reinterpret_cast<bf16x4*>(lx + 2 * C::XPL + off) = l;
-      }
-    }
-  };
+  auto load_x = [&](int k0) { x6_load_x<C>(a, tl, xrows, tid, k0, xr); };
+  auto store_x = [&]() { x6_store_x<C>(lx, tid, xr); };
   // stage src_st's 18 pieces into slot `slot`: wave w copies pieces w, w+4, ...; a wave with
   // fewer than PPW repeats its last piece (same bytes, same place) so every wave issues PPW
   // (buffer loads to LDS, not global_load_lds: see k_c3x6p's load_w)
@@ -1029,14 +828,7 @@ __global__ __launch_bounds__(256, 2) void k_c3x6h(FwdArgs a) {
     for (int j = 0; j < C::PPW; ++j) {
       int piece = wave + j * C::WAVES;
       if (piece >= C::PIECES) piece -= C::WAVES;
-#if DN_X6_GDMA
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(wimg) +
-                                                          (long)src_st * C::WSTP * 2 + piece * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(dst + piece * 1024), 16, 0, 0);
-#else
       buf_lds16(wrs, dst + piece * 1024, src_st * C::WSTP * 2 + piece * 1024 + lane * 16);
-#endif
     }
   };
 
@@ -1059,10 +851,11 @@ __global__ __launch_bounds__(256, 2) void k_c3x6h(FwdArgs a) {
     const int mode = (tail && c + 1 == nch) ? tail : 0;
     // MT = 4: the A pieces of two rows at a time (registers), the B fragments read once for all
     constexpr int MH = MT >= 4 ? 2 : MT;
-    // MT = 4 keeps the per-block form (its 2 x 48 accumulators at NT = 6 leave no room for accl)
-    constexpr bool BLK = MT >= 4 && !(DN_X6H_CARRY4 && NT <= 3);
-    constexpr int QG = MT >= 4 ? 1 : x6_qgc(MT, NT), NG = NT / QG,
-                  LOOK = NG < DN_X6H_LOOK ? NG : DN_X6H_LOOK;
+    // MT = 4 keeps the per-block form at NT = 6 (its 2 x 48 accumulators leave no room for
+    // accl); with NT <= 3 it carries the corrections too (96 accumulator VGPRs)
+    constexpr bool BLK = MT >= 4 && NT > 3;
+    // B fragment groups are read LOOK = 2 ahead of their MFMAs
+    constexpr int QG = MT >= 4 ? 1 : x6_qgc(MT, NT), NG = NT / QG, LOOK = NG < 2 ? NG : 2;
     bf16x8 bv[3][NT];
     auto read_b = [&](int g) {
 #pragma unroll
@@ -1133,7 +926,9 @@ __global__ __launch_bounds__(256, 2) void k_c3x6h(FwdArgs a) {
       for (int g = 0; g < NG; ++g) {
         if constexpr (BLK) x6_group<MH, NT, QG>(acch, av, bv, g * QG);
         else x6_group_c<MH, NT, QG>(acch, acclh, av, bv, g * QG);
-        if constexpr (MT >= 4 || DN_X6H_PIN) {  // the block sums' adds here, not sunk to the stage end
+        // MT = 4: the block sums' adds here, not sunk to the stage end (MT = 2's hi adds pinned
+        // per group the same way measured 1-2 % slower at 100->96 @256^2)
+        if constexpr (MT >= 4) {
 #pragma unroll
           for (int i = 0; i < MH; ++i)
 #pragma unroll
@@ -1349,7 +1144,6 @@ __device__ __forceinline__ void pk_deconv_x6(const PackJob& j, long e) {
 
 // raw deconv weight W[ci][co][a][b] (96, 96, 2, 2) -> the data gradient's pre-split images: per
 // input-channel half h and parity, [plane][K block (32 co)][row = ci - 48h][32 co] (X6_DG_BF each)
-constexpr int X6_DG_BF = 3 * 3 * 48 * 32;
 __device__ __forceinline__ void pk_deconv_dgrad_x6(const PackJob& j, long e) {
   const int h = (int)(e / (4 * X6_DG_BF)), par = (int)(e / X6_DG_BF) % 4, r0 = (int)(e % X6_DG_BF);
   const int p = r0 / (3 * 48 * 32), row = (r0 / 32) % (3 * 48), k = r0 % 32;  // row = kb*48 + ci'
@@ -1491,12 +1285,9 @@ long x6_pack_elems(int K, int nout, int zc) {
 }
 
 // DN_X6_W6=1/0: 96- and 48-output-channel large-grid launches on the Winograd kernel or not
-// (default DN_X6_W6_DEFAULT)
-#ifndef DN_X6_W6_DEFAULT
-#define DN_X6_W6_DEFAULT 1
-#endif
+// (default: on)
 static bool w6_enabled() {
-  static const bool on = getenv("DN_X6_W6") ? atoi(getenv("DN_X6_W6")) != 0 : DN_X6_W6_DEFAULT != 0;
+  static const bool on = !getenv("DN_X6_W6") || atoi(getenv("DN_X6_W6")) != 0;
   return on;
 }
 
@@ -1670,6 +1461,8 @@ hipError_t launch_fwd_x6(const FwdArgs& a, hipStream_t s) {
 
 
 // ------------------------------------------------------------------------------------
+// (k_wgrad3s shares this file with the forward kernels for the compiler's sake: built without
+// it, k_c3x6p<6,0,true>'s epilogue selects other scalar instructions for min(48, NOUT - cz))
 // 3x3 weight gradient at fp32 accuracy on the bf16 matrix cores (k_wgrad3s: 96 or 48 output
 // channels).  GEMM M = output channels, N = input channels x 9 taps, K = pixels.  Each 32-pixel
 // K stage of the gradient G [px][GS] and of the input X [(sh+2) rows][sw+2][XS] (halo included;
@@ -1982,696 +1775,6 @@ hipError_t launch_gwgrad_x6(const WgradArgs& a0, int splits, hipStream_t s) {
   if (ct == 64) return run_wgrad3s<2, 1, 4>(a, splits, s, nz);
   if (ct == 32) return run_wgrad3s<2, 1, 2>(a, splits, s, nz);
   return run_wgrad3s<2, 1, 3>(a, splits, s, nz);
-}
-
-// ------------------------------------------------------------------------------------
-// The nin head (nin_a -> nin_b -> nin_c, arch_unet.py:186-190, 257-259) on the activated
-// dec_conv1b output, with the two 96x96 1x1 GEMMs in the bf16x6 arithmetic.  As in k_nin_head
-// the tile lives in the 16x16 MFMA C/D map (rows = channels, columns = 16 pixels), which is
-// directly the B operand of the next GEMM: for K block b (32 channels) lane group g supplies
-// channels {32b + 4g + r, 32b + 16 + 4g + r} (r < 4) = registers 2b and 2b+1 of its tile
-// fragment, split into three bf16x8 planes in registers.  The weight images are pre-split
-// in the same permuted K order (pk_head_x6: [plane][b][out][32], 64-B rows, quads
-// swizzled) and DMA'd into LDS once per workgroup (54 KiB per layer).
-// ------------------------------------------------------------------------------------
-// Persistent: one 8-wave workgroup per CU keeps both images (108 KiB) and the biases / nin_c
-// weights in LDS for the whole launch; wave-tiles are single 16-pixel rows, taken in a wave-
-// strided loop, the next row's input loaded into registers while the current one computes
-// (the images are read from L2 once per CU, not once per tile).
-// SAVE: na / nb written for the backward; PAIR: the input is a pair image (hd.rd); B1: plain
-// bf16 products (the bf16 base's autocast arithmetic): the input rounded to bf16, the images'
-// leading planes (the weights rounded to bf16), one MFMA per block chained in fp32
-// IBF (with B1): the input activation is stored as bf16 (FwdArgs::in_bf16), 8 bytes per lane and
-// 4 channels, taken as the operand without conversion
-template <bool SAVE, bool PAIR, bool B1 = false, bool IBF = false>
-__global__ __launch_bounds__(512, 1) void k_nin_head_x6(FwdArgs a, HeadArgs hd, const __bf16* wimg,
-                                                      int nwt) {
-  static_assert(!IBF || B1, "bf16 input only in the plain-bf16 head");
-  __shared__ __attribute__((aligned(16))) __bf16 lw[2 * X6_HEAD_BF];
-  __shared__ __attribute__((aligned(16))) float lb[2 * 96 + X6_HEAD_OCMAX * 97];  // ba|bb|wc|bc
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  for (int q = wave; q < 2 * X6_HEAD_BF * 2 / 1024; q += 8)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(wimg + q * 512 + lane * 8),
-        (__attribute__((address_space(3))) void*)(lw + q * 512), 16, 0, 0);
-  for (int e = threadIdx.x; e < 2 * 96 + hd.oc * 97; e += 512) {
-    float v;
-    if (e < 96) v = hd.ba[e];
-    else if (e < 192) v = hd.bb[e - 96];
-    else if (e < 192 + hd.oc * 96) v = hd.wc[e - 192];
-    else v = hd.bc[e - 192 - hd.oc * 96];
-    lb[e] = v;
-  }
-  const float* lbc = lb + 192 + hd.oc * 96;
-  const int tiles_x = (a.OW + 15) / 16;
-  const int wstride = gridDim.x * 8;
-  // per-row buffer resources, out-of-range offsets instead of branches (see k_deconv_x6)
-  const long in_row = (long)a.IWt * a.in_stride;
-  auto load = [&](int wt, f32x4 (&v)[6], int& rd) {
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x, gx = (r - gy * tiles_x) * 16 + li;
-    const bool ok = wt < nwt && gx < a.OW;
-    constexpr int EB = IBF ? 2 : 4;  // bytes per stored activation
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.in) +
-                                   (((long)n * a.IHt + gy) * in_row + a.in_off) * EB),
-        (short)0, (int)(in_row * EB), 0x00020000);
-    const int off = ok ? (gx * a.in_stride + 4 * lg) * EB : 0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      if constexpr (IBF) {  // bf16 bits of channels 16q + 4lg .. +3 in v[q][0..1]
-        typedef unsigned u32x2h __attribute__((ext_vector_type(2)));
-        const u32x2h d = __builtin_bit_cast(u32x2h, __builtin_amdgcn_raw_buffer_load_b64(rs, off + 32 * q, 0, 0));
-        v[q] = f32x4{__uint_as_float(d[0]), __uint_as_float(d[1]), 0.f, 0.f};
-      } else {
-        v[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 64 * q, 0, 0));
-      }
-    }
-    if constexpr (PAIR) {  // the cell's pair choice, loaded with the row (no wait of its own later)
-      const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<unsigned char*>(hd.rd + ((long)n * a.OH + gy) * (a.OW / 2)), (short)0,
-          a.OW / 2, 0x00020000);
-      rd = __builtin_amdgcn_raw_buffer_load_b8(rr, ok ? gx >> 1 : 0x7fffffff, 0, 0);
-    }
-  };
-  auto bias_act = [](f32x4& v, float4 b) {
-    v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * 0.2f;
-  };
-  auto save = [&](float* dst, long row, int off, const f32x4& v, int q) {  // 16 px x 96 ch
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst + row * a.OW * 96, (short)0,
-                                                                        a.OW * 96 * 4, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, off + 64 * q, 0, 0);
-  };
-  // out = W (LDS image at `img`) x in, three 32-channel K blocks of six split products each
-  // (INB: `in` holds bf16 bits as loaded by load() under IBF)
-  auto gemm96 = [&](auto inb_tag, const __bf16* img, const f32x4 (&in)[6], f32x4 (&out)[6][1]) {
-    constexpr bool INB = decltype(inb_tag)::value;
-#pragma unroll
-    for (int f = 0; f < 6; ++f) out[f][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      bf16x8 xv[3][1];
-      const float v8[8] = {in[2 * b][0], in[2 * b][1], in[2 * b][2], in[2 * b][3],
-                           in[2 * b + 1][0], in[2 * b + 1][1], in[2 * b + 1][2], in[2 * b + 1][3]};
-      if constexpr (B1) {
-        if constexpr (INB) {
-          const u32x4_t d = {__float_as_uint(in[2 * b][0]), __float_as_uint(in[2 * b][1]),
-                             __float_as_uint(in[2 * b + 1][0]), __float_as_uint(in[2 * b + 1][1])};
-          xv[0][0] = __builtin_bit_cast(bf16x8, d);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) xv[0][0][j] = (__bf16)v8[j];
-        }
-#pragma unroll
-        for (int f = 0; f < 6; ++f) {
-          const int row = b * 96 + f * 16 + li;
-          const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(img + row * 32 + x6_swz(row, lg) * 8);
-          out[f][0] = mfma_bf16(w0, xv[0][0], out[f][0]);
-        }
-        continue;
-      }
-      split3x8(v8, xv[0][0], xv[1][0], xv[2][0]);
-      bf16x8 wv[3][6];
-#pragma unroll
-      for (int f = 0; f < 6; ++f) {
-        const int row = b * 96 + f * 16 + li;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          wv[pl][f] = *reinterpret_cast<const bf16x8*>(img + (pl * 3 * 96 + row) * 32 + x6_swz(row, lg) * 8);
-      }
-      x6_block<6, 1, 1>(out, wv, xv);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // one wave-tile; two register sets (xa, xb) alternate so that the next tile's loads are in
-  // flight while this one computes and no copy forces a wait for them (or for the stores)
-  auto tile = [&](int wt, const f32x4 (&xin)[6], int rd) {
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x, gx = (r - gy * tiles_x) * 16 + li;
-    const bool ok = gx < a.OW;
-    const long row = (long)n * a.OH + gy;
-    const int soff = ok ? (gx * 96 + 4 * lg) * 4 : 0x7fffffff;
-    f32x4 u[6][1], h[6];
-    gemm96(std::integral_constant<bool, IBF>{}, lw, xin, u);  // nin_a
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-      bias_act(u[f][0], *reinterpret_cast<const float4*>(lb + f * 16 + 4 * lg));
-      h[f] = u[f][0];
-    }
-    if constexpr (SAVE)
-#pragma unroll
-      for (int f = 0; f < 6; ++f) save(hd.na, row, soff, h[f], f);
-    gemm96(std::false_type{}, lw + X6_HEAD_BF, h, u);  // nin_b
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-      bias_act(u[f][0], *reinterpret_cast<const float4*>(lb + 96 + f * 16 + 4 * lg));
-      if constexpr (SAVE) save(hd.nb, row, soff, u[f][0], f);
-    }
-    // nin_c (fp32 VALU): per-lane partial over its 24 channels, then across the lane groups;
-    // lane group 0 stores (the others get an out-of-range offset)
-    // PAIR: pair image pixel (gy, gx) -> pixel pair[rd][gx & 1] of cell (gy, gx / 2), i.e. y's
-    // rows 2gy, 2gy + 1
-    int yoff = 0x7fffffff;
-    if (lg == 0 && ok) {
-      if constexpr (PAIR) {
-        constexpr unsigned kPair = 0xB721ED84u;
-        const int k = (kPair >> (4 * (rd & 7) + 2 * (gx & 1))) & 3;
-        yoff = ((k >> 1) * a.OW + (gx & ~1) + (k & 1)) * 4;
-      } else {
-        yoff = gx * 4;
-      }
-    }
-    constexpr int YR = PAIR ? 2 : 1;  // y rows per wave-tile
-    for (int o = 0; o < hd.oc; ++o) {
-      float t = 0.f;
-#pragma unroll
-      for (int f = 0; f < 6; ++f) {
-        const float4 w = *reinterpret_cast<const float4*>(lb + 192 + o * 96 + f * 16 + 4 * lg);
-        t = fmaf(w.x, u[f][0][0], t); t = fmaf(w.y, u[f][0][1], t);
-        t = fmaf(w.z, u[f][0][2], t); t = fmaf(w.w, u[f][0][3], t);
-      }
-      t += __shfl_xor(t, 16);
-      t += __shfl_xor(t, 32);
-      const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-          hd.y + (((long)n * hd.oc + o) * YR * a.OH + YR * gy) * a.OW, (short)0, YR * a.OW * 4,
-          0x00020000);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t + lbc[o]), ry, yoff, 0, 0);
-    }
-  };
-  int wt = blockIdx.x * 8 + wave;
-  f32x4 xa[6], xb[6];
-  int ra = 0, rb = 0;
-  load(wt, xa, ra);
-  __syncthreads();  // images, biases and nin_c weights landed
-  for (; wt < nwt; wt += 2 * wstride) {
-    load(wt + wstride, xb, rb);
-    tile(wt, xa, ra);
-    if (wt + wstride >= nwt) break;
-    load(wt + 2 * wstride, xa, ra);
-    tile(wt + wstride, xb, rb);
-  }
-}
-
-
-// ------------------------------------------------------------------------------------
-// Backward of the fused head in the bf16x6 arithmetic (k_head_bwd's products on the fp32
-// matrix cores, arch_unet.py:186-190 differentiated):
-//   g_nb = leaky'(nb) * (Wc^T dy)      (fp32 VALU, K = oc, nin_c's weights in LDS)
-//   g_na = leaky'(na) * (Wb^T g_nb)    (bf16x6 GEMM, image Wb^T)
-//   g_d1b = leaky'(d1b) * (Wa^T g_na)  (bf16x6 GEMM, image Wa^T)
-// The tile stays in the MFMA C/D map (rows = channels, columns = 16 pixels), which is the B
-// operand of the next GEMM as in k_nin_head_x6; the transposed images (pk_head_x6 with flip) are
-// DMA'd into LDS once per workgroup.  One 8-wave workgroup per CU walks 16-pixel wave-tiles of
-// the flattened pixel range; a tile's nb / dy / na / d1b loads are issued together at its start
-// (the other wave on the SIMD computes meanwhile).  Every 16-pixel tile addresses its rows
-// through its own buffer resource (pixel ranges beyond 2 GiB, out-of-range lanes read zeros and
-// drop their stores).
-// ------------------------------------------------------------------------------------
-template <int OCM>  // nin_c outputs at most (registers of dy)
-__global__ __launch_bounds__(512, 1) void k_head_bwd_x6(HeadBwdArgs h, const __bf16* wimg, long nwt) {
-  __shared__ __attribute__((aligned(16))) __bf16 lw[2 * X6_HEAD_BF];
-  __shared__ __attribute__((aligned(16))) float lc[X6_HEAD_OCMAX * 96];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  for (int q = wave; q < 2 * X6_HEAD_BF * 2 / 1024; q += 8)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(wimg + q * 512 + lane * 8),
-        (__attribute__((address_space(3))) void*)(lw + q * 512), 16, 0, 0);
-  for (int e = threadIdx.x; e < h.oc * 96; e += 512) lc[e] = h.wc[e];
-  __syncthreads();
-  auto rsrc = [&](const float* base, long px0, int npx_t) {  // 16 pixels x 96 channels
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + px0 * 96), (short)0,
-                                             npx_t * 96 * 4, 0x00020000);
-  };
-  auto mask = [](f32x4& v, const f32x4& m) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = m[r] > 0.f ? v[r] : v[r] * 0.2f;
-  };
-  // out = W (LDS image at `img`) x in: three 32-channel K blocks of six split products each
-  // (k_nin_head_x6's gemm96)
-  auto gemm96 = [&](const __bf16* img, const f32x4 (&in)[6], f32x4 (&out)[6][1]) {
-#pragma unroll
-    for (int f = 0; f < 6; ++f) out[f][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      bf16x8 xv[3][1];
-      const float v8[8] = {in[2 * b][0], in[2 * b][1], in[2 * b][2], in[2 * b][3],
-                           in[2 * b + 1][0], in[2 * b + 1][1], in[2 * b + 1][2], in[2 * b + 1][3]};
-      split3x8(v8, xv[0][0], xv[1][0], xv[2][0]);
-      bf16x8 wv[3][6];
-#pragma unroll
-      for (int f = 0; f < 6; ++f) {
-        const int row = b * 96 + f * 16 + li;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          wv[pl][f] = *reinterpret_cast<const bf16x8*>(img + (pl * 3 * 96 + row) * 32 + x6_swz(row, lg) * 8);
-      }
-      x6_block<6, 1, 1>(out, wv, xv);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  const int loff = (li * 96 + 4 * lg) * 4;  // lane's bytes within a tile row set
-  for (long wt = (long)blockIdx.x * 8 + wave; wt < nwt; wt += (long)gridDim.x * 8) {
-    const long px0 = wt * 16;
-    const int npx_t = h.npx - px0 < 16 ? (int)(h.npx - px0) : 16;
-    const bool ok = li < npx_t;
-    const int off = ok ? loff : 0x7fffffff;
-    const __amdgpu_buffer_rsrc_t rnb = rsrc(h.nb, px0, npx_t), rna = rsrc(h.na, px0, npx_t),
-                                 rd1 = rsrc(h.d1b, px0, npx_t);
-    f32x4 nb[6], na[6], d1[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-      nb[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rnb, off + 64 * q, 0, 0));
-    float dy[OCM];
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(h.dy + px0 * h.dy_stride), (short)0, npx_t * h.dy_stride * 4, 0x00020000);
-#pragma unroll
-    for (int o = 0; o < OCM; ++o)
-      if (o < h.oc)
-        dy[o] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                              rdy, ok ? (li * h.dy_stride + o) * 4 : 0x7fffffff, 0, 0));
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-      na[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rna, off + 64 * q, 0, 0));
-    // g_nb (K = oc, k_head_bwd's order)
-    f32x4 t[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) t[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int o = 0; o < OCM; ++o) {
-      if (o >= h.oc) break;
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        const float4 w = *reinterpret_cast<const float4*>(lc + o * 96 + q * 16 + 4 * lg);
-        t[q][0] = fmaf(w.x, dy[o], t[q][0]); t[q][1] = fmaf(w.y, dy[o], t[q][1]);
-        t[q][2] = fmaf(w.z, dy[o], t[q][2]); t[q][3] = fmaf(w.w, dy[o], t[q][3]);
-      }
-    }
-    // (h.g_nb null: k_wgrad1p<., GNB> recomputes g_nb from dy and nb, nothing stores it)
-    const __amdgpu_buffer_rsrc_t wnb = rsrc(h.g_nb ? h.g_nb : h.nb, px0, h.g_nb ? npx_t : 0);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      mask(t[q], nb[q]);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, t[q]), wnb, off + 64 * q, 0, 0);
-    }
-    f32x4 u[6][1];
-    gemm96(lw, t, u);  // Wb^T g_nb
-    // d1b's loads behind the first GEMM (registers), in flight during the second
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-      d1[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rd1, off + 64 * q, 0, 0));
-    const __amdgpu_buffer_rsrc_t wna = rsrc(h.g_na, px0, npx_t);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      mask(u[q][0], na[q]);
-      t[q] = u[q][0];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, t[q]), wna, off + 64 * q, 0, 0);
-    }
-    gemm96(lw + X6_HEAD_BF, t, u);  // Wa^T g_na
-    const __amdgpu_buffer_rsrc_t wd1 = rsrc(h.g_d1b, px0, npx_t);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      mask(u[q][0], d1[q]);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, u[q][0]), wd1, off + 64 * q, 0, 0);
-    }
-  }
-}
-
-// wimg = pack_job_head_bwd_x6's images; every tensor NHWC stride 96 (dy: dy_stride, oc <=
-// X6_HEAD_BWD_OCMAX: dy in registers; more outputs spill, k_head_bwd takes them)
-hipError_t launch_head_bwd_x6(const HeadBwdArgs& h, const void* wimg, hipStream_t s) {
-  if (h.oc < 1 || h.oc > X6_HEAD_BWD_OCMAX || h.npx < 1 || h.dy_stride < h.oc) return hipErrorInvalidValue;
-  const long nwt = (h.npx + 15) / 16;
-  const long blocks = (nwt + 7) / 8 < 256 ? (nwt + 7) / 8 : 256;  // one workgroup per CU
-  prof_kernel("k_head_bwd_x6<4>");
-  hipLaunchKernelGGL(k_head_bwd_x6<4>, dim3((unsigned)blocks), dim3(512), 0, s, h,
-                     static_cast<const __bf16*>(wimg), nwt);
-  return hipGetLastError();
-}
-
-// nin_a / nin_b weights (OIHW 96x96x1x1, contiguous) -> the two pre-split head images
-hipError_t launch_pack_head_x6(const float* wa, const float* wb, void* out, hipStream_t s) {
-  PackBatch b;
-  b.j[b.n++] = pack_job_head_x6(wa, wb, out);
-  return pack_flush(b, s);
-}
-
-hipError_t launch_nin_head_x6(const FwdArgs& a, const HeadArgs& h, const void* wimg, hipStream_t s,
-                              bool bf16) {
-  if ((bf16 && (h.rd || (h.na && h.nb))) || (a.in_bf16 && !bf16) || a.K != 96 || h.oc < 1 ||
-      h.oc > X6_HEAD_OCMAX || ((a.in_stride | a.in_off) & 3) ||
-      (long)a.IWt * a.in_stride * 4 >= 0x7fffffffL || (long)a.OW * 96 * 4 * 2 >= 0x7fffffffL)
-    return hipErrorInvalidValue;
-  const long nwt = (long)a.N * a.OH * ((a.OW + 15) / 16);  // one 16-pixel row per wave-tile
-  if (nwt >= (1L << 31) - (1L << 20)) return hipErrorInvalidValue;
-  long blocks = (nwt + 7) / 8;
-  if (blocks > 256) blocks = 256;  // one workgroup per CU
-  const __bf16* w = static_cast<const __bf16*>(wimg);
-  const dim3 grid((unsigned)blocks), block(512);
-  const bool save = h.na && h.nb;
-  if (save && h.rd) return hipErrorInvalidValue;  // the pair pass saves nothing
-  if (h.rd) hipLaunchKernelGGL((k_nin_head_x6<false, true>), grid, block, 0, s, a, h, w, (int)nwt);
-  else if (save) hipLaunchKernelGGL((k_nin_head_x6<true, false>), grid, block, 0, s, a, h, w, (int)nwt);
-  else if (bf16 && a.in_bf16)
-    hipLaunchKernelGGL((k_nin_head_x6<false, false, true, true>), grid, block, 0, s, a, h, w, (int)nwt);
-  else if (bf16) hipLaunchKernelGGL((k_nin_head_x6<false, false, true>), grid, block, 0, s, a, h, w, (int)nwt);
-  else hipLaunchKernelGGL((k_nin_head_x6<false, false>), grid, block, 0, s, a, h, w, (int)nwt);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// ConvTranspose2d(96, 96, 2, 2) forward (UpsampleCat's deconv, arch_unet.py:51-62) in the
-// bf16x6 arithmetic: out(2y+a, 2x+b, co) = bias[co] + sum_ci x(y, x, ci) W[ci][co][a][b].
-// Each parity's 96x96 weight matrix is pre-split ([plane][K block][co][32 ci], 64-B rows,
-// swizzled quads; 54 KiB) and DMA'd into LDS.  A lane's B operand is 8 consecutive input
-// channels of its pixel (two float4 loads, split in registers); the 16x16 C/D tile (rows =
-// output channels, columns = pixels) is stored as float4 channel quads at the scattered
-// output pixel.
-// ------------------------------------------------------------------------------------
-// Persistent: one 8-wave workgroup per CU holds two parity images, (a, 0) and (a, 1), waves 0-3 /
-// 4-7 computing those parities; the two workgroups of a group (blockIdx.x bit 3 = a, the other
-// bits = group; same XCD) cover the four parities of the same wave-tiles -- one low-res row of
-// 16 pixels -- so three of the four reads of an input row hit that XCD's L2.  The next row's
-// input is loaded into registers while the current one computes; the images are read from L2
-// once per workgroup.
-// B1: plain bf16 products (the bf16 base's autocast arithmetic, as k_nin_head_x6's B1): the input
-// rounded to bf16, the images' leading planes (the weights rounded to bf16), one MFMA per block
-// chained in fp32 -- a sixth of the MFMAs, so the launch is bound by its output stores
-template <bool B1 = false>
-__global__ __launch_bounds__(512, 1) void k_deconv_x6(FwdArgs a, const __bf16* wimg, int nwt) {
-  __shared__ __attribute__((aligned(16))) __bf16 lw[2 * X6_HEAD_BF];
-  __shared__ __attribute__((aligned(16))) float lbias[96];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  const int pa = (blockIdx.x >> 3) & 1, pb = wave >> 2, wq = wave & 3;
-  const int grp = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7), ngrp = gridDim.x >> 1;
-  const __bf16* src = wimg + 2 * pa * X6_HEAD_BF;  // parities 2a, 2a + 1
-  for (int q = wave; q < 2 * X6_HEAD_BF * 2 / 1024; q += 8)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(src + q * 512 + lane * 8),
-        (__attribute__((address_space(3))) void*)(lw + q * 512), 16, 0, 0);
-  if (threadIdx.x < 96) lbias[threadIdx.x] = a.bias[threadIdx.x];
-  const __bf16* img = lw + pb * X6_HEAD_BF;
-  const int tiles_x = (a.OW + 15) / 16;
-  const int wstride = ngrp * 4;
-  // loads and stores through per-row buffer resources: out-of-range lanes (past the row or the
-  // last wave-tile) get an out-of-range offset instead of a branch, so every wave-tile issues the
-  // same 6 loads and 6 stores and the compiler's counted waits cover exactly the loads they need.
-  // Constant offsets go into the vector offset (folded into the instruction's offset field), never
-  // into soffset: a 16-byte buffer store with an SGPR soffset whose data registers were rewritten
-  // by the very next instruction (an LDS read) stored a corrupted last dword on some lanes.
-  const long in_row = (long)a.IWt * a.in_stride, out_row = 2L * a.OW * a.out_stride;
-  auto load = [&](int wt, float4 (&v)[6]) {
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x, gx = (r - gy * tiles_x) * 16 + li;
-    const bool ok = wt < nwt && gx < a.OW;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.in + ((long)n * a.IHt + gy) * in_row + a.in_off), (short)0,
-        (int)(in_row * 4), 0x00020000);
-    const int off = ok ? (gx * a.in_stride + 8 * lg) * 4 : 0x7fffffff;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      v[2 * b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * b, 0, 0));
-      v[2 * b + 1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * b + 16, 0, 0));
-    }
-  };
-  // one wave-tile; two register sets alternate (see k_nin_head_x6)
-  auto tile = [&](int wt, const float4 (&xin)[6]) {
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x, gx = (r - gy * tiles_x) * 16 + li;
-    f32x4 out[6][1];
-#pragma unroll
-    for (int f = 0; f < 6; ++f) out[f][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float4 u0 = xin[2 * b], u1 = xin[2 * b + 1];
-      const float v8[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-      if constexpr (B1) {
-        bf16x8 x0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x0[j] = (__bf16)v8[j];
-#pragma unroll
-        for (int f = 0; f < 6; ++f) {
-          const int row = b * 96 + f * 16 + li;
-          const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(img + row * 32 + x6_swz(row, lg) * 8);
-          out[f][0] = mfma_bf16(w0, x0, out[f][0]);
-        }
-        continue;
-      }
-      bf16x8 xv[3][1];
-      split3x8(v8, xv[0][0], xv[1][0], xv[2][0]);
-      // one output fragment at a time, its three weight planes read one fragment ahead: 24
-      // operand registers live instead of 72, which leaves room for the third input set below
-      bf16x8 wv[2][3];
-      auto read_w = [&](int f, bf16x8 (&w)[3]) {
-        const int row = b * 96 + f * 16 + li;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          w[pl] = *reinterpret_cast<const bf16x8*>(img + (pl * 3 * 96 + row) * 32 + x6_swz(row, lg) * 8);
-      };
-      read_w(0, wv[0]);
-#pragma unroll
-      for (int f = 0; f < 6; ++f) {
-        if (f + 1 < 6) read_w(f + 1, wv[(f + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        // x6_group's product order (hi = w0 x0; lo = w0 x1, w1 x0, w0 x2, w1 x1, w2 x0)
-        const bf16x8(&w)[3] = wv[f & 1];
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 hi = mfma_bf16(w[0], xv[0][0], z);
-        f32x4 lo = mfma_bf16(w[0], xv[1][0], z);
-        lo = mfma_bf16(w[1], xv[0][0], lo);
-        lo = mfma_bf16(w[0], xv[2][0], lo);
-        lo = mfma_bf16(w[1], xv[1][0], lo);
-        lo = mfma_bf16(w[2], xv[0][0], lo);
-        x6_acc_add(out[f][0], hi, lo);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        a.out + ((long)n * 2 * a.OH + 2 * gy + pa) * out_row + a.out_off, (short)0,
-        (int)(out_row * 4), 0x00020000);
-    // Whole 128-B lines per store: a lane holds 4 channels of fragments f and f + 1 of its own
-    // pixel, so one store per fragment wrote only 64 B of each pixel's 32-channel line, and the
-    // L2 filled the other half from HBM before the second store came (0.75 GB of extra fetch per
-    // 256^2 launch, profiles/r5a_pmc_step.json).  Adjacent lanes (pixels 2p, 2p + 1 of the
-    // wave-tile) swap one fragment's registers (DPP quad_perm [1,0,3,2]), and each store
-    // instruction writes the full line (channels 32k .. 32k + 31) of one pixel per lane pair:
-    // the even lane its fragment-f quad, the odd lane the even pixel's fragment-(f + 1) quad.
-    const bool ev = (li & 1) == 0;
-    const int gxa = gx - (li & 1);  // the pair's even pixel; gxa + 1 the odd one
-    const int offa = gxa < a.OW ? ((2 * gxa + pb) * a.out_stride + 4 * lg + (ev ? 0 : 16)) * 4 : 0x7fffffff;
-    const int offb = gxa + 1 < a.OW ? ((2 * gxa + 2 + pb) * a.out_stride + 4 * lg + (ev ? 0 : 16)) * 4
-                                     : 0x7fffffff;
-#pragma unroll
-    for (int f = 0; f < 6; f += 2) {
-      const float4 b0 = *reinterpret_cast<const float4*>(lbias + f * 16 + 4 * lg);
-      const float4 b1 = *reinterpret_cast<const float4*>(lbias + f * 16 + 16 + 4 * lg);
-      const f32x4 o0 = {out[f][0][0] + b0.x, out[f][0][1] + b0.y, out[f][0][2] + b0.z, out[f][0][3] + b0.w};
-      const f32x4 o1 = {out[f + 1][0][0] + b1.x, out[f + 1][0][1] + b1.y, out[f + 1][0][2] + b1.z,
-                        out[f + 1][0][3] + b1.w};
-      f32x4 t;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        t[r] = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
-                                             __builtin_bit_cast(int, ev ? o1[r] : o0[r]), 0xB1, 0xF, 0xF, false));
-      const f32x4 va = ev ? o0 : t, vb = ev ? t : o1;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, va), rs, offa + 64 * f, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, vb), rs, offb + 64 * f, 0, 0);
-    }
-  };
-  // three input register sets: a wave-tile's input is requested two tiles before it is used
-  // (one tile of MFMA work did not cover the HBM latency: 0.8 ms at 64 x 128^2 -> 256^2 against
-  // ~0.4 ms of HBM traffic)
-  int wt = grp * 4 + wq;
-  float4 xa[6], xb[6], xc[6];
-  load(wt, xa);
-  load(wt + wstride, xb);
-  __syncthreads();  // parity images and bias landed
-  for (; wt < nwt; wt += 3 * wstride) {
-    load(wt + 2 * wstride, xc);
-    tile(wt, xa);
-    if (wt + wstride >= nwt) break;
-    load(wt + 3 * wstride, xa);
-    tile(wt + wstride, xb);
-    if (wt + 2 * wstride >= nwt) break;
-    load(wt + 4 * wstride, xb);
-    tile(wt + 2 * wstride, xc);
-  }
-}
-
-bool deconv_x6_ok(const FwdArgs& a) {  // float4 views; per-row buffer extents below 2^31 bytes
-  return a.K == 96 && a.NOUT == 96 && !((a.in_stride | a.in_off | a.out_stride | a.out_off) & 3) &&
-         (long)a.IWt * a.in_stride * 4 < 0x7fffffffL && 2L * a.OW * a.out_stride * 4 < 0x7fffffffL;
-}
-
-// raw deconv weight (96, 96, 2, 2) -> four pre-split parity images (4 x X6_HEAD_BF bf16)
-hipError_t launch_pack_deconv_x6(const float* w, void* out, hipStream_t s) {
-  PackBatch b;
-  b.j[b.n++] = pack_job_deconv_x6(w, out);
-  return pack_flush(b, s);
-}
-
-// a: in = x (IHt = OH = h, IWt = OW = w), out = the 2h x 2w view, bias; K = NOUT = 96; b1: plain
-// bf16 products (the bf16 base)
-hipError_t launch_deconv_x6(const FwdArgs& a, const void* wimg, hipStream_t s, bool b1) {
-  if (!deconv_x6_ok(a)) return hipErrorInvalidValue;
-  const long nwt = (long)a.N * a.OH * ((a.OW + 15) / 16);  // one low-res 16-pixel row per wave-tile
-  if (nwt >= (1L << 31) - (1L << 20)) return hipErrorInvalidValue;
-  // groups of two workgroups (one per parity row a), a multiple of 8 groups (one per XCD)
-  long groups = (nwt + 3) / 4;
-  if (groups > 128) groups = 128;
-  groups = (groups + 7) / 8 * 8;
-  if (b1) {
-    prof_kernel("k_deconv_x6<true>");
-    hipLaunchKernelGGL(k_deconv_x6<true>, dim3((unsigned)(2 * groups)), dim3(512), 0, s, a,
-                       static_cast<const __bf16*>(wimg), (int)nwt);
-  } else {
-    prof_kernel("k_deconv_x6<false>");
-    hipLaunchKernelGGL(k_deconv_x6<false>, dim3((unsigned)(2 * groups)), dim3(512), 0, s, a,
-                       static_cast<const __bf16*>(wimg), (int)nwt);
-  }
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------
-// Data gradient of the 96-channel ConvTranspose2d(2, 2) (arch_unet.py:51-62) in the bf16x6
-// arithmetic: dx(y, x, ci) = sum_{a,b} sum_co dy(2y+a, 2x+b, co) W[ci][co][a][b] (x leaky'(mask)),
-// a GEMM with K = 4 parities x 96.  Persistent, one 8-wave workgroup per CU holding the images of
-// one input-channel half h for all four parities (4 x 27 KiB; the two halves' workgroups of a
-// group share an XCD and the same wave-tiles, so the second read of dy hits L2); a wave-tile is
-// one row of 16 output pixels x 48 channels, computed in four parity steps whose dy rows are
-// loaded one step ahead (two alternating register sets), the mask with the last step.
-// ------------------------------------------------------------------------------------
-template <bool MASKED>
-__global__ __launch_bounds__(512, 1) void k_deconv_dgrad_x6(FwdArgs a, const __bf16* wimg, int nwt) {
-  __shared__ __attribute__((aligned(16))) __bf16 lw[4 * X6_DG_BF];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 15, lg = lane >> 4;
-  const int h = (blockIdx.x >> 3) & 1;
-  const int grp = ((blockIdx.x >> 4) << 3) | (blockIdx.x & 7), ngrp = gridDim.x >> 1;
-  const __bf16* src = wimg + (long)h * 4 * X6_DG_BF;
-  for (int q = wave; q < 4 * X6_DG_BF * 2 / 1024; q += 8)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(src + q * 512 + lane * 8),
-        (__attribute__((address_space(3))) void*)(lw + q * 512), 16, 0, 0);
-  const int tiles_x = (a.OW + 15) / 16;
-  const int wstride = ngrp * 8;
-  // per-row buffer resources, constant offsets in the vector offset (see k_deconv_x6)
-  const long in_row = (long)a.IWt * a.in_stride;
-  auto load = [&](int wt, int par, float4 (&v)[6]) {  // dy row 2gy + a, pixels 2gx + b
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x, gx = (r - gy * tiles_x) * 16 + li;
-    const bool ok = wt < nwt && gx < a.OW;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.in + ((long)n * a.IHt + 2 * gy + (par >> 1)) * in_row + a.in_off),
-        (short)0, (int)(in_row * 4), 0x00020000);
-    const int off = ok ? ((2 * gx + (par & 1)) * a.in_stride + 8 * lg) * 4 : 0x7fffffff;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      v[2 * b] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * b, 0, 0));
-      v[2 * b + 1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 128 * b + 16, 0, 0));
-    }
-  };
-  auto row_rsrc = [&](const float* base, int stride, int wt) {  // output-resolution row of wt
-    const int n = wt / (a.OH * tiles_x), r = wt - n * a.OH * tiles_x;
-    const int gy = r / tiles_x;
-    return __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(base + ((long)n * a.OH + gy) * a.OW * stride), (short)0,
-        a.OW * stride * 4, 0x00020000);
-  };
-  auto pix_off = [&](int wt, int stride, int coff) {  // this lane's channel quad, or out of range
-    const int r = wt % (a.OH * tiles_x), gx = (r % tiles_x) * 16 + li;
-    return wt < nwt && gx < a.OW ? (gx * stride + coff + 48 * h + 4 * lg) * 4 : 0x7fffffff;
-  };
-  auto mload = [&](int wt, float4 (&m)[3]) {
-    const __amdgpu_buffer_rsrc_t rs = row_rsrc(a.mask, a.mask_stride, wt);
-    const int off = pix_off(wt, a.mask_stride, a.mask_off);
-#pragma unroll
-    for (int f = 0; f < 3; ++f)
-      m[f] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + 64 * f, 0, 0));
-  };
-  auto step = [&](int par, const float4 (&xin)[6], f32x4 (&acc)[3][1]) {
-    const __bf16* img = lw + par * X6_DG_BF;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const float4 u0 = xin[2 * b], u1 = xin[2 * b + 1];
-      const float v8[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-      bf16x8 xv[3][1];
-      split3x8(v8, xv[0][0], xv[1][0], xv[2][0]);
-      bf16x8 wv[3][3];
-#pragma unroll
-      for (int f = 0; f < 3; ++f) {
-        const int row = b * 48 + f * 16 + li;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          wv[pl][f] = *reinterpret_cast<const bf16x8*>(img + (pl * 3 * 48 + row) * 32 + x6_swz(row, lg) * 8);
-      }
-      x6_block<3, 1, 1>(acc, wv, xv);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // the running sums materialised here: otherwise the compiler defers the fp32 adds of the
-    // block sums to the epilogue and keeps every step's MFMA results live (it spills)
-#pragma unroll
-    for (int f = 0; f < 3; ++f) asm volatile("" : "+v"(acc[f][0]));
-  };
-  auto epilogue = [&](int wt, const f32x4 (&acc)[3][1], const float4 (&m)[3]) {
-    const __amdgpu_buffer_rsrc_t rs = row_rsrc(a.out, a.out_stride, wt);
-    const int off = pix_off(wt, a.out_stride, a.out_off);
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-      float4 o = make_float4(acc[f][0][0], acc[f][0][1], acc[f][0][2], acc[f][0][3]);
-      if constexpr (MASKED) {
-        o.x *= m[f].x > 0.f ? 1.f : 0.2f; o.y *= m[f].y > 0.f ? 1.f : 0.2f;
-        o.z *= m[f].z > 0.f ? 1.f : 0.2f; o.w *= m[f].w > 0.f ? 1.f : 0.2f;
-      }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rs, off + 64 * f, 0, 0);
-    }
-  };
-  int wt = grp * 8 + wave;
-  float4 xa[6], xb[6], m[3] = {};
-  load(wt, 0, xa);
-  __syncthreads();  // images landed
-  for (; wt < nwt; wt += wstride) {
-    f32x4 acc[3][1];
-#pragma unroll
-    for (int f = 0; f < 3; ++f) acc[f][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    load(wt, 1, xb);
-    step(0, xa, acc);
-    load(wt, 2, xa);
-    step(1, xb, acc);
-    load(wt, 3, xb);
-    if constexpr (MASKED) mload(wt, m);
-    step(2, xa, acc);
-    load(wt + wstride, 0, xa);
-    step(3, xb, acc);
-    epilogue(wt, acc, m);
-  }
-}
-
-bool deconv_dgrad_x6_ok(const FwdArgs& a) {  // float4 views; per-row buffer extents below 2^31
-  return a.K == 96 && a.NOUT == 96 && a.IHt == 2 * a.OH && a.IWt == 2 * a.OW &&
-         !((a.in_stride | a.in_off | a.out_stride | a.out_off) & 3) &&
-         (a.epi == EPI_PLAIN || (a.epi == EPI_MASK && a.mask && !((a.mask_stride | a.mask_off) & 3))) &&
-         (long)a.IWt * a.in_stride * 4 < 0x7fffffffL && (long)a.OW * a.out_stride * 4 < 0x7fffffffL &&
-         (a.epi != EPI_MASK || (long)a.OW * a.mask_stride * 4 < 0x7fffffffL);
-}
-
-hipError_t launch_deconv_dgrad_x6(const FwdArgs& a, const void* wimg, hipStream_t s) {
-  if (!deconv_dgrad_x6_ok(a)) return hipErrorInvalidValue;
-  const long nwt = (long)a.N * a.OH * ((a.OW + 15) / 16);  // one 16-pixel output row per wave-tile
-  if (nwt >= (1L << 31) - (1L << 20)) return hipErrorInvalidValue;
-  // groups of two workgroups (one per input-channel half), a multiple of 8 groups (one per XCD)
-  long groups = (nwt + 7) / 8;
-  if (groups > 128) groups = 128;
-  groups = (groups + 7) / 8 * 8;
-  const dim3 grid((unsigned)(2 * groups)), block(512);
-  const __bf16* w = static_cast<const __bf16*>(wimg);
-  if (a.epi == EPI_MASK) hipLaunchKernelGGL(k_deconv_dgrad_x6<true>, grid, block, 0, s, a, w, (int)nwt);
-  else hipLaunchKernelGGL(k_deconv_dgrad_x6<false>, grid, block, 0, s, a, w, (int)nwt);
-  return hipGetLastError();
 }
 
 }  // namespace dn

@@ -139,6 +139,8 @@ struct HeadBwdArgs {
 constexpr int HEAD_WS = 100;   // k-row stride of a head weight image (conflict-free A reads)
 constexpr int HEAD_LW = 9728;  // 96 * HEAD_WS rounded up to 256 floats
 constexpr int X6_HEAD_BF = 3 * 3 * 96 * 32;  // bf16 per layer of the bf16x6 head image (54 KiB)
+// bf16 per (input-channel half, parity) image of the bf16x6 deconv data gradient (pk_deconv_dgrad_x6)
+constexpr int X6_DG_BF = 3 * 3 * 48 * 32;
 constexpr int X6_HEAD_OCMAX = 16;  // most nin_c outputs of the bf16x6 head (kept in its LDS)
 constexpr int X6_HEAD_BWD_OCMAX = 4;  // most nin_c outputs of its backward (k_head_bwd_x6)
 
@@ -323,7 +325,7 @@ hipError_t launch_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s);
 hipError_t launch_nin_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s);
 hipError_t launch_pack_head(const WView& wa, const WView& wb, float* out, hipStream_t s,
                             PackBatch* pb = nullptr);  // pb: queued, not launched
-// bf16x6 nin head (conv_x6.hip): pre-split nin_a | nin_b images (2 x X6_HEAD_BF bf16)
+// bf16x6 nin head (head_x6.hip): pre-split nin_a | nin_b images (2 x X6_HEAD_BF bf16)
 hipError_t launch_pack_head_x6(const float* wa, const float* wb, void* out, hipStream_t s);
 // bf16: plain bf16 products (the bf16 base; no saved activations, no pair image)
 hipError_t launch_nin_head_x6(const FwdArgs& a, const HeadArgs& h, const void* wimg, hipStream_t s,
@@ -332,7 +334,7 @@ hipError_t launch_nin_head_x6(const FwdArgs& a, const HeadArgs& h, const void* w
 // 2x2 cell only (a.sel_rd): output = the "pair image" [N][OH/2][OW][96] NHWC, column 2j + s = pixel
 // pair[rd][s] of cell j (s = 0, 1), i.e. exactly the pixels training_script.md:141-144 reads
 hipError_t launch_fwd_x6_sel(const FwdArgs& a, hipStream_t s);
-// bf16x6 ConvTranspose2d(96, 96, 2, 2) forward: four pre-split parity images (4 x X6_HEAD_BF bf16)
+// bf16x6 ConvTranspose2d(96, 96, 2, 2) forward (deconv_x6.hip): four pre-split parity images (4 x X6_HEAD_BF bf16)
 bool deconv_x6_ok(const FwdArgs& a);
 hipError_t launch_pack_deconv_x6(const float* w, void* out, hipStream_t s);
 hipError_t launch_deconv_x6(const FwdArgs& a, const void* wimg, hipStream_t s, bool b1 = false);

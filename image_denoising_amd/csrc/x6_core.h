@@ -1,6 +1,7 @@
 // Shared bf16x6 building blocks: exact three-way bf16 split of fp32 operands and the
 // six-product 16x16x32 MFMA block (used by the conv forward / data-gradient kernels in
-// conv_x6.hip and by the 3x3 weight-gradient kernel in conv.hip).  See conv_x6.hip's header.
+// conv_x6.hip, the head and deconv kernels in head_x6.hip / deconv_x6.hip and the weight-gradient
+// kernels in wgrad_x6p.hip).  See conv_x6.hip's header.
 #pragma once
 
 #include "conv_epi.h"
@@ -77,7 +78,7 @@ __device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, con
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// acc += hi + lo as scalar v_add_f32 (conv_x6.hip is built with -fno-slp-vectorize): a packed
+// acc += hi + lo as scalar v_add_f32 (the bf16x6 files are built with -fno-slp-vectorize): a packed
 // v_pk_add_f32 beside MFMAs costs more issue cycles than the two scalar adds it replaces
 // (A/B on one box: k_wgrad3s 96->96 at 64 x 128^2 1.127 -> 1.050 ms, the step 25.2 -> 24.8-25.1 ms)
 __device__ __forceinline__ void x6_acc_add(f32x4& acc, const f32x4& hi, const f32x4& lo) {
