@@ -91,6 +91,9 @@ SIGNATURES = {
     "dn_conv2d_x6_pack_size": (c_size_t, [c_int, c_int, c_int]),
     "dn_conv2d_forward_x6": (c_int, [_F, c_int, c_int, c_int, c_int, c_int, _F, _F, c_int, c_int,
                                      _F, c_int, c_void_p, c_size_t, c_void_p]),
+    "dn_upconv3_x6_pack_size": (c_size_t, []),
+    "dn_upconv3_forward_x6": (c_int, [_F, c_int, c_int, c_int, c_int, _F, c_int, _F, _F, _F, _F, _F,
+                                      c_int, c_void_p, c_size_t, c_void_p]),
     "dn_conv2d_backward_data_x6": (c_int, [_F, c_int, c_int, c_int, c_int, _F, c_int, _F, c_int,
                                            c_int, _F, c_int, c_void_p, c_size_t, c_void_p]),
     "dn_conv2d_backward_data": (c_int, [_F, c_int, c_int, c_int, c_int, _F, c_int, c_int, _F,

@@ -584,6 +584,31 @@ dn_status dn_conv2d_forward_x6(const float* x, int x_stride, int N, int H, int W
   return hip_status(e, "dn_conv2d_forward_x6");
 }
 
+size_t dn_upconv3_x6_pack_size(void) { return (size_t)UPC_BYTES; }
+
+dn_status dn_upconv3_forward_x6(const float* xlo, int xlo_stride, int N, int h, int w,
+                                const float* img, int C, const float* w3, const float* b3,
+                                const float* wd, const float* bd, float* y, int y_stride,
+                                void* pack_ws, size_t pack_bytes, void* stream) {
+  if (!xlo || !img || !w3 || !b3 || !wd || !bd || !y) return fail(DN_ERR_ARG, "null argument");
+  if (N < 1 || h < 1 || w < 1 || C < 1 || C > 4 || xlo_stride < 96 || y_stride < 96 ||
+      ((xlo_stride | y_stride) & 3))
+    return fail(DN_ERR_ARG, "bad shape (1 <= C <= 4, strides >= 96 and multiples of 4)");
+  if (dn_status st = need_pack(pack_ws, pack_bytes, dn_upconv3_x6_pack_size())) return st;
+  hipStream_t s = (hipStream_t)stream;
+  PackBatch pb;
+  pb.j[pb.n++] = pack_job_upconv_x6(w3, b3, wd, bd, C, pack_ws);
+  hipError_t e = pack_flush(pb, s);
+  if (e == hipSuccess) {
+    FwdArgs a = fwd_args(View{const_cast<float*>(xlo), xlo_stride, 0}, h, w, N, 2 * h, 2 * w, 96 + C,
+                         96, View{y, y_stride, 0}, OUT_NHWC);
+    a.wp = static_cast<const float*>(pack_ws); a.in_t1 = img; a.epi = EPI_BIAS_ACT;
+    const OpTimer timer(s, "fwd3", 2.0 * (96 + C) * 96 * 9 * N * 4 * h * w, 96 + C, 96, 2 * h, 2 * w, N);
+    e = launch_upconv3_x6(a, s);
+  }
+  return hip_status(e, "dn_upconv3_forward_x6");
+}
+
 dn_status dn_conv2d_backward_data_x6(const float* dz, int N, int H, int W, int Cout,
                                      const float* w, int Cin, const float* mask, int mask_stride,
                                      int accumulate, float* dx, int dx_stride, void* pack_ws,

@@ -1154,6 +1154,65 @@ __device__ __forceinline__ void pk_deconv_dgrad_x6(const PackJob& j, long e) {
                               x6_swz(row, k >> 3) * 8 + (k & 7)] = p == 0 ? hh : (p == 1 ? m : l);
 }
 
+// dec_conv1a(up1(.)) composed for k_upconv3_x6 (upconv_x6.hip; the image's layout: dn_internal.h).
+// UpsampleCat has no activation between its deconv and the concat, so on the 96 up1 channels the
+// 3x3 conv of the deconv's output is, per output parity (py, px), a 2x2-tap conv of the deconv's
+// input: tap (ky, kx) reads high-resolution pixel (Y + ky - 1, X + kx - 1) = low-resolution pixel
+// (y + dy, x + dx), dy = floor((py + ky - 1) / 2), at deconv parity (py + ky - 1) & 1, so
+//   Weff[py][px][dy][dx][o][i] = sum_{(ky, kx) -> (dy, dx)} sum_c W3[o][c][ky][kx] Wd[i][c][a][b],
+// summed in fp64, rounded once to fp32 and split exactly.  The deconv's bias reaches an output
+// pixel through its in-range taps only: one 96-vector per (row class, column class) of the pixel
+// (first / interior / last), b3 included.  The image channels' weights are K-packed:
+// k = slot + 6 (c + C tap), slot = the split product (h,h) (h,m) (m,h) (h,l) (l,h) (m,m).
+__device__ __forceinline__ void pk_upconv_x6(const PackJob& j, long e) {
+  const int ctot = j.K, C = j.K - 96;
+  const float* w3 = j.w;
+  const float* wd = j.w2;
+  if (e < UPC_W_BF / 3) {
+    const int i = (int)(e % 96), o = (int)(e / 96 % 96), tap = (int)(e / 9216 % 4), par = (int)(e / 36864);
+    const int py = par >> 1, px = par & 1, ty = tap >> 1, tx = tap & 1;
+    double s = 0.0;
+    for (int ky = 0; ky < 3; ++ky) {
+      if (((py + ky + 1) >> 1) - 1 != py - 1 + ty) continue;  // floor((py + ky - 1) / 2)
+      for (int kx = 0; kx < 3; ++kx) {
+        if (((px + kx + 1) >> 1) - 1 != px - 1 + tx) continue;
+        const int ab = 2 * ((py + ky + 1) & 1) + ((px + kx + 1) & 1);
+        const float* a3 = w3 + (long)o * ctot * 9 + 3 * ky + kx;
+        const float* ad = wd + (long)i * 96 * 4 + ab;
+        for (int c = 0; c < 96; ++c) s += (double)a3[c * 9] * (double)ad[c * 4];
+      }
+    }
+    __bf16 h, m, l;
+    split3((float)s, h, m, l);
+    __bf16* out = static_cast<__bf16*>(j.out) +
+                  ((long)((par * 4 + tap) * 3 + (i >> 5)) * 3 * 96 + o) * 32 + (i & 31);
+    out[0] = h;
+    out[96 * 32] = m;
+    out[2 * 96 * 32] = l;
+    return;
+  }
+  e -= UPC_W_BF / 3;
+  if (e < UPC_X_BF) {
+    const int k = (int)(e / (96 * 32)) * 32 + (int)(e % 32), o = (int)(e / 32 % 96);
+    const int slot = k % 6, ct = k / 6, c = ct % C, tap = ct / C;
+    __bf16 h = (__bf16)0.f, m = h, l = h;
+    if (tap < 9) split3(w3[((long)o * ctot + 96 + c) * 9 + tap], h, m, l);
+    static_cast<__bf16*>(j.out)[UPC_W_BF + e] = slot == 2 || slot == 5 ? m : (slot == 4 ? l : h);
+    return;
+  }
+  e -= UPC_X_BF;
+  const int o = (int)(e % 96), rx = (int)(e / 96 % 3), ry = (int)(e / 288);
+  double s = j.w3[o];
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx) {
+      if ((ry == 0 && ky == 0) || (ry == 2 && ky == 2) || (rx == 0 && kx == 0) || (rx == 2 && kx == 2))
+        continue;
+      const float* a3 = w3 + (long)o * ctot * 9 + 3 * ky + kx;
+      for (int c = 0; c < 96; ++c) s += (double)a3[c * 9] * (double)j.w4[c];
+    }
+  reinterpret_cast<float*>(static_cast<__bf16*>(j.out) + UPC_W_BF + UPC_X_BF)[e] = (float)s;
+}
+
 // launch_pack_bf16's image (k_pack_bf16, conv_bf16.hip): [chunk][ky][kx][n][40], zero padded
 __device__ __forceinline__ void pk_bf16(const PackJob& j, long e) {
   const int NP = j.g0, WST = j.g1, spc = j.g2 ? 3 : 1;
@@ -1186,6 +1245,7 @@ __global__ __launch_bounds__(256) void k_pack_batch(PackBatch b) {
       case PK_HEAD_X6: pk_head_x6(j, e); break;
       case PK_DECONV_DGRAD_X6: pk_deconv_dgrad_x6(j, e); break;
       case PK_BF16: pk_bf16(j, e); break;
+      case PK_UPCONV_X6: pk_upconv_x6(j, e); break;
       default: static_cast<float*>(j.out)[e] = 0.f; break;
     }
   }
@@ -1235,6 +1295,13 @@ PackJob pack_job_head_bwd_x6(const float* wa, const float* wb, void* out) {
 PackJob pack_job_deconv_x6(const float* w, void* out) {
   PackJob j{};
   j.kind = PK_DECONV_X6; j.w = w; j.out = out;
+  return j;
+}
+
+PackJob pack_job_upconv_x6(const float* w3, const float* b3, const float* wd, const float* bd,
+                           int C, void* out) {
+  PackJob j{};
+  j.kind = PK_UPCONV_X6; j.w = w3; j.w2 = wd; j.w3 = b3; j.w4 = bd; j.K = 96 + C; j.out = out;
   return j;
 }
 

@@ -141,6 +141,15 @@ constexpr int HEAD_LW = 9728;  // 96 * HEAD_WS rounded up to 256 floats
 constexpr int X6_HEAD_BF = 3 * 3 * 96 * 32;  // bf16 per layer of the bf16x6 head image (54 KiB)
 // bf16 per (input-channel half, parity) image of the bf16x6 deconv data gradient (pk_deconv_dgrad_x6)
 constexpr int X6_DG_BF = 3 * 3 * 48 * 32;
+// k_upconv3_x6's image (upconv_x6.hip, pk_upconv_x6): the 16 composed 96 x 96 matrices
+// [parity][tap][32-channel block][plane][96 o][32 i] (bf16), the image channels' K-packed
+// split-product weights [K block < 7][96 o][32] (bf16), the bias table [3 x 3 border class][96]
+// (fp32)
+constexpr int UPC_W_BF = 16 * 3 * 3 * 96 * 32;
+constexpr int UPC_XKB = 7;  // K blocks of 32 for 9 taps x 6 products x (<= 4) image channels
+constexpr int UPC_X_BF = UPC_XKB * 96 * 32;
+constexpr int UPC_BIAS_F = 9 * 96;
+constexpr long UPC_BYTES = 2L * (UPC_W_BF + UPC_X_BF) + 4L * UPC_BIAS_F;
 constexpr int X6_HEAD_OCMAX = 16;  // most nin_c outputs of the bf16x6 head (kept in its LDS)
 constexpr int X6_HEAD_BWD_OCMAX = 4;  // most nin_c outputs of its backward (k_head_bwd_x6)
 
@@ -210,17 +219,19 @@ struct FwdGeom { int KC, TAPS, WNS, LW; };
 // images of a 96-channel deconv, the two bf16x6 head images, and a zero fill (the weight
 // gradients' 64-float DMA padding).  Strides of the weight view are element strides (< 2^31).
 enum PackKind { PK_F32 = 0, PK_X6 = 1, PK_DECONV_X6 = 2, PK_HEAD_X6 = 3, PK_ZERO = 4,
-                PK_DECONV_DGRAD_X6 = 5, PK_BF16 = 6, PK_W6 = 7 };
+                PK_DECONV_DGRAD_X6 = 5, PK_BF16 = 6, PK_W6 = 7, PK_UPCONV_X6 = 8 };
 struct PackJob {
   const float* w;   // view origin (WView.w + off); PK_HEAD_X6: nin_a, PK_DECONV_X6: raw weight
   const float* w2;  // PK_HEAD_X6: nin_b
+  const float* w3;  // PK_UPCONV_X6: w = the conv's weight, w2 = the deconv's, w3 / w4 = their
+  const float* w4;  // biases; K = the conv's input channels (96 + image channels)
   void* out;
   int sK, sN, sT, sZ, taps, flip;
   int kind, K, NOUT, nz, zc, ntot, nch, tail;
   int g0, g1, g2, g3;  // PK_F32: KC, TAPS, WNS, LW; PK_X6: NP; PK_ZERO: floats;
                        // PK_BF16: NP, stage elements, 3x3?, image elements
 };
-constexpr int kPackJobs = 24;  // 24 x 104 B of kernel arguments
+constexpr int kPackJobs = 24;  // 24 x 120 B of kernel arguments
 struct PackBatch {
   PackJob j[kPackJobs];
   int n = 0;
@@ -236,6 +247,7 @@ __host__ __device__ inline long pack_job_elems(const PackJob& j) {
     case PK_HEAD_X6: return 2L * 3 * 3 * 96 * 32;
     case PK_DECONV_DGRAD_X6: return 4L * 3 * 3 * 96 * 32;
     case PK_BF16: return j.g3;
+    case PK_UPCONV_X6: return UPC_W_BF / 3 + UPC_X_BF + UPC_BIAS_F;
     default: return j.g0;
   }
 }
@@ -248,6 +260,14 @@ hipError_t launch_head_bwd_x6(const HeadBwdArgs& h, const void* wimg, hipStream_
 PackJob pack_job_deconv_x6(const float* w, void* out);
 PackJob pack_job_deconv_dgrad_x6(const float* w, void* out);
 PackJob pack_job_zero(float* out, int n);
+// dec_conv1a(up1(.)) composed (upconv_x6.hip): w3 (96, 96 + C, 3, 3), b3, wd (96, 96, 2, 2), bd
+PackJob pack_job_upconv_x6(const float* w3, const float* b3, const float* wd, const float* bd,
+                           int C, void* out);
+// the fused launch: a.in = the low-resolution 96-channel view (IHt x IWt), a.in_t1 = the NCHW
+// network input at OH x OW = 2 IHt x 2 IWt, a.K = 96 + C, a.NOUT = 96, a.wp = the image above,
+// a.out NHWC; bias, both layers' weights and LeakyReLU are in the image / the kernel
+bool upconv3_x6_ok(const FwdArgs& a);
+hipError_t launch_upconv3_x6(const FwdArgs& a, hipStream_t s);
 // the bf16 image of launch_pack_bf16 (conv_bf16.hip) as a job of the pass's pack launch
 bool pack_job_bf16(const WView& wv, int K, int nout, int ksize, void* out, PackJob& j);
 

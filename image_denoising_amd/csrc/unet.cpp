@@ -168,8 +168,9 @@ bool build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, Plan& p, st
     }
     p.packX[i] = alloc_f((e + 1) / 2);
   }
-  p.packXV = p.w6s_list = p.w6s_cnt = -1;
+  p.packXV = p.w6s_list = p.w6s_cnt = p.packUC = -1;
   if (!bwd) {
+    p.packUC = alloc_f((UPC_BYTES + 3) / 4);
     p.packXV = alloc_f((x6_pack_elems(96, 96, 0) + 1) / 2);
     p.w6s_list = alloc_f(2L * N * (H / 2) * (W / 2));
     p.w6s_cnt = alloc_f(2L * N);
@@ -517,6 +518,13 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
     return launch_fwd_bf16(a, st, 1);
   };
 
+  // Forward-only bf16x6 plans from the grid size k_c3w6 takes dec_conv1a at: up1 and dec_conv1a
+  // as ONE launch (k_upconv3_x6: the deconv composed into the conv's 96 up1 channels, 2x2 taps
+  // per output parity over d2b; nothing else reads up1 without a backward).  DN_UP1_FUSE=0: the
+  // two launches (A/B)
+  static const bool up1_fuse_env = !getenv("DN_UP1_FUSE") || atoi(getenv("DN_UP1_FUSE")) != 0;
+  const bool up1_fuse = up1_fuse_env && x6 && !p.with_bwd && p.packUC >= 0 && nf == 48 && C <= 4 &&
+                        (x6_tail_f(D1A) & X6_W6);
   // every weight image of the pass (fp32, bf16x6 and bf16 alike) in one pack launch (not for a
   // prepacked forward: dn_unet_pack_weights left them in ws)
   if (pack != RUN_ONLY) {
@@ -526,7 +534,11 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
       const Layer& L = p.P.L[i];
       const float* w = prm + L.woff;
       PackJob j;
-      if (L.deconv && deconv_x6_layer(i)) {
+      if (up1_fuse && (i == UP1 || i == D1A)) {  // one composed image for the pair
+        if (i == D1A)
+          DN_TRY(add(true, pack_job_upconv_x6(w, Bs(D1A), prm + p.P.L[UP1].woff, Bs(UP1), C,
+                                              ws + p.packUC)));
+      } else if (L.deconv && deconv_x6_layer(i)) {
         DN_TRY(add(true, pack_job_deconv_x6(w, ws + p.packUX[i])));
       } else if (L.deconv && bf16) {  // ConvTranspose2d [cin][cout][2][2]: a 1x1 image per parity
         const long img = bf16_pack_elems(L.cin, L.cout, 1);
@@ -587,7 +599,7 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
                            // 16 scattered bytes per 512-B pixel cost the launch 0.19 ms/step; c1's
                            // channels [2nf, c1s) then hold stale data, which the debug-buffer
                            // contract in denoise_hip.h states)
-                           x6 && (x6_tail_f(D1A) & X6_T1) ? nullptr : ws + p.c1, p.c1s, 2 * nf,
+                           x6 && ((x6_tail_f(D1A) & X6_T1) || up1_fuse) ? nullptr : ws + p.c1, p.c1s, 2 * nf,
                            p.c1kp, p.with_bwd ? ws + p.xin : nullptr, s, enc0_bf16));
   {  // enc_conv1 + pool1 -> skip slice of c2
     const View pv = V(p.c[1], p.cs[1], 2 * nf);
@@ -621,8 +633,16 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
     DN_TRY(conv_forward(ib, V(p.da[l], 2 * nf), 1, V(p.db[l], 2 * nf), OUT_NHWC, s));
   }
   // up1: d2b -> c1[0:2nf]
-  DN_TRY(deconv_forward(UP1, V(p.db[1], 2 * nf), V(p.c1, p.c1s, 0), s));
-  DN_TRY(conv_forward(D1A, V(p.c1, p.c1s), 1, V(p.d1a, 96), OUT_NHWC, s));
+  if (up1_fuse) {  // (the record carries dec_conv1a's algorithmic FLOPs, as the Winograd launches)
+    FwdArgs a = fwd_args(V(p.db[1], 2 * nf), H(1), Wd(1), N, H(0), Wd(0), p.c1k, 96, V(p.d1a, 96),
+                         OUT_NHWC);
+    a.wp = ws + p.packUC; a.in_t1 = x; a.epi = EPI_BIAS_ACT;
+    DN_TIMED(s, "fwd3", 2.0 * N * H(0) * Wd(0) * p.c1k * 96 * 9, p.c1k, 96, H(0), Wd(0), N,
+             launch_upconv3_x6(a, s));
+  } else {
+    DN_TRY(deconv_forward(UP1, V(p.db[1], 2 * nf), V(p.c1, p.c1s, 0), s));
+    DN_TRY(conv_forward(D1A, V(p.c1, p.c1s), 1, V(p.d1a, 96), OUT_NHWC, s));
+  }
   // the head kernels' common arguments (their input: the activated dec_conv1b output, 96 -> 96)
   auto head_in = [&](long off, int h) {
     return fwd_args(V(off, 96), N, h, Wd(0), 96, 96, none, OUT_NHWC);

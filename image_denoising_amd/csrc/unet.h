@@ -47,6 +47,7 @@ struct Plan {
   // tap-transposed PK_W6 image (y tiles) and the per-orientation cell lists (2 N cells uint32)
   // with their counts (2 N int); -1 in plans with a backward
   long packXV, w6s_list, w6s_cnt;
+  long packUC;                  // k_upconv3_x6's image (forward-only plans; -1: none)
   long fwd_floats;
   // gradients
   long g_nb, g_na, g_d1b, g_d1a, g_c1;

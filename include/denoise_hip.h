@@ -289,6 +289,17 @@ dn_status dn_conv2d_backward_data_x6(const float* dz, int N, int H, int W, int C
                                      const float* w, int Cin, const float* mask, int mask_stride,
                                      int accumulate, float* dx, int dx_stride, void* pack_ws,
                                      size_t pack_bytes, void* stream);
+/* dec_conv1a(cat(up1(xlo), img)) of arch_unet.py:51-62, 250-252 as one launch (forward-only
+   plans): ConvTranspose2d(96, 96, 2, 2) composed with the 3x3 conv's 96 up1 channels into 2x2 taps
+   per output parity over xlo, the C <= 4 image channels a 3x3 conv of img, LeakyReLU(0.2).
+   xlo: NHWC [N,h,w] x 96 channels, pixel stride xlo_stride; img: NCHW [N,C,2h,2w]; w3:
+   [96,96+C,3,3], b3: [96]; wd: [96,96,2,2] (in,out,2,2), bd: [96]; y: NHWC [N,2h,2w] x 96, pixel
+   stride y_stride (strides multiples of 4). */
+size_t dn_upconv3_x6_pack_size(void);
+dn_status dn_upconv3_forward_x6(const float* xlo, int xlo_stride, int N, int h, int w,
+                                const float* img, int C, const float* w3, const float* b3,
+                                const float* wd, const float* bd, float* y, int y_stride,
+                                void* pack_ws, size_t pack_bytes, void* stream);
 /* dx = conv^T(dz) [* leaky'(mask)] : data gradient (mask nullable; mask_stride). If accumulate,
    dx += result.  dx stride dx_stride. */
 dn_status dn_conv2d_backward_data(const float* dz, int N, int H, int W, int Cout, const float* w,
