@@ -142,6 +142,17 @@ SIGNATURES = {
                                        c_size_t, c_int, c_void_p]),
     "dn_iunet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
                                        POINTER(c_int64), c_int, POINTER(c_int)]),
+    "dn_groupnorm_scratch_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_groupnorm_forward": (c_int, [_F, c_int, c_int, _F, c_int, c_int, _F, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_int, _F, _F, c_int, _F, c_void_p,
+                                     c_size_t, c_void_p]),
+    "dn_groupnorm_backward": (c_int, [_F, c_int, c_int, _F, c_int, c_int, _F, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, _F, _F, _F, _F, c_void_p,
+                                      c_size_t, c_void_p]),
+    "dn_conv2d_wgrad_blocked_slab_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dn_conv2d_backward_weight_blocked": (c_int, [_F, c_int, c_int, _F, c_int, c_int, c_int, c_int,
+                                                  c_int, c_int, c_int, c_int, c_int, c_int, _F,
+                                                  c_void_p, c_void_p]),
     "dn_adapter_param_count": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "dn_adapter_forward": (c_int, [_F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dn_adapter_slab_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -1415,6 +1415,7 @@ hipError_t launch_gwgrad(int mode, const WgradArgs& a0, int splits, hipStream_t 
   }
   // 1x1: the asynchronous k_wgrad1 tiled over (input-channel block of 96, output-channel block)
   const dim3 grid(splits, (a.Cin + 95) / 96, (a.Cout + cb - 1) / cb);
+  prof_kernel(cb == 96 ? "k_wgrad1<6,6,2,2>" : "k_wgrad1<3,6,1,3>");
   if (cb == 96) hipLaunchKernelGGL((k_wgrad1<6, 6, 2, 2>), grid, dim3(256), 0, s, a, 0);
   else hipLaunchKernelGGL((k_wgrad1<3, 6, 1, 3>), grid, dim3(192), 0, s, a, 0);
   return hipGetLastError();

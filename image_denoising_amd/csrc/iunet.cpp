@@ -236,6 +236,62 @@ void wgrad_jobs(const IParams& P, std::vector<WJob>& v) {
 
 }  // namespace
 
+// ---- GroupNorm and the blocked weight gradient: launch sequences shared with capi.cpp ------
+long gn_part_doubles(int N, long P, int C) { return 2L * N * chan_sums_splits(N, P) * C; }
+
+dn_status gn_forward(const View& z, int N, long P, int C, int G, const float* gamma,
+                     const float* beta, int act, const View* res, const View& y, float* stats,
+                     double* part, float* scale, float* shift, hipStream_t s) {
+  const int S = chan_sums_splits(N, P);
+  IU_TRY(launch_chan_sums(z, nullptr, N, P, C, S, part, s));
+  IU_TRY(launch_gn_fwd_fin(part, S, N, C, G, P, GN_EPS, gamma, beta, stats, scale, shift, s));
+  IU_TRY(launch_affine(z, nullptr, scale, nullptr, shift, act, res, y, N, P, C, s));
+  return DN_OK;
+}
+
+dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G,
+                      const float* gamma, const float* stats, const View& dz, float* dgamma,
+                      float* dbeta, double* part, float* ca, float* cb, float* cc, hipStream_t s) {
+  const int S = chan_sums_splits(N, P);
+  IU_TRY(launch_chan_sums(dy, &z, N, P, C, S, part, s));
+  IU_TRY(launch_gn_bwd_fin(part, S, N, C, G, P, gamma, stats, ca, cb, cc, dgamma, dbeta, s));
+  IU_TRY(launch_affine(dy, &z, ca, cb, cc, 0, nullptr, dz, N, P, C, s));
+  return DN_OK;
+}
+
+// every layer's slab rows hold [W ; b] (the bias row is there whether the layer has one or not)
+long gwgrad_slab_floats(int mode, int N, int h, int w, int cin, int cout) {
+  const int taps = mode == W_C3 ? 9 : 1;
+  return (long)gwgrad_splits(mode, N, h, w, cin, cout) * ((long)cout * cin * taps + cout);
+}
+
+dn_status gwgrad_run(int mode, const View& g, const View& x, int N, int h, int w, int cin,
+                     int cout, bool bias, int prec, float* dwb, float* slab, hipStream_t s) {
+  if (!gwgrad_ok(mode, cin, cout, g, x)) {
+    set_error("no blocked weight-gradient kernel for this layer shape or these views");
+    return DN_ERR_ARG;
+  }
+  const int taps = mode == W_C3 ? 9 : 1;
+  const long n = (long)cout * cin * taps + (bias ? cout : 0);
+  WgradArgs a{};
+  a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
+  a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
+  a.N = N; a.KH = h; a.KW = w; a.Cout = cout; a.Cin = cin;
+  a.zeros = slab; a.slab = slab + 64; a.slab_stride = n;
+  a.wlayout = 0; a.cin_total = cin; a.ci_base = 0; a.bias = bias ? 1 : 0;
+  int sp = gwgrad_splits(mode, N, h, w, cin, cout);
+  IU_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s));
+  // fp32_x6: the 3x3 weight gradients on the bf16x6 kernel too
+  if (prec == DN_PREC_FP32_X6 && mode == W_C3 && gwgrad_x6_ok(a)) {
+    sp = gwgrad_x6_splits(a, sp);
+    IU_TRY(launch_gwgrad_x6(a, sp, s));
+  } else {
+    IU_TRY(launch_gwgrad(mode, a, sp, s));
+  }
+  IU_TRY(launch_reduce(slab + 64, n, sp, n, dwb, s));
+  return DN_OK;
+}
+
 bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err) {
   if (c.in_nc < 1 || c.in_nc > 3 || c.out_nc < 1 || c.out_nc > 4) {
     err = "ImprovedUNet: in_nc must be 1..3 and out_nc 1..4";
@@ -397,11 +453,8 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
     std::vector<WJob> jobs;
     wgrad_jobs(P, jobs);
     long slab = 0;
-    for (const WJob& j : jobs) {
-      const int taps = j.mode == W_C3 ? 9 : 1;
-      const int sp = gwgrad_splits(j.mode, N, H >> j.lvl, W >> j.lvl, j.cin, j.cout);
-      slab = std::max(slab, (long)sp * ((long)j.cout * j.cin * taps + j.cout));
-    }
+    for (const WJob& j : jobs)
+      slab = std::max(slab, gwgrad_slab_floats(j.mode, N, H >> j.lvl, W >> j.lvl, j.cin, j.cout));
     const int st = enc0_wgrad_splits(N, H, W);
     slab = std::max(slab, (long)st * (48L * (P.C + 1) * 9 + 48));
     p.slab = off;
@@ -563,16 +616,9 @@ dn_status gn_fwd(const Ctx& c, const IGN& g, const View& z, int h, int w, float*
                  const View* res, const View& out) {
   if (c.dry) return DN_OK;
   OpScope prof(c.s, "gn", g.C, 1, 1, h, w, c.p.N, 0.0);
-  const int N = c.p.N;
-  const long P = (long)h * w;
-  const int S = chan_sums_splits(N, P);
-  double* part = reinterpret_cast<double*>(c.ws + c.p.gpart);
-  IU_TRY(launch_chan_sums(z, nullptr, N, P, g.C, S, part, c.s));
-  IU_TRY(launch_gn_fwd_fin(part, S, N, g.C, g.G, P, GN_EPS, c.prm + g.g, c.prm + g.b, stats,
-                           c.ws + c.p.sc, c.ws + c.p.sh, c.s));
-  IU_TRY(launch_affine(z, nullptr, c.ws + c.p.sc, nullptr, c.ws + c.p.sh, act, res, out, N, P, g.C,
-                       c.s));
-  return DN_OK;
+  return gn_forward(z, c.p.N, (long)h * w, g.C, g.G, c.prm + g.g, c.prm + g.b, act, res, out, stats,
+                    reinterpret_cast<double*>(c.ws + c.p.gpart), c.ws + c.p.sc, c.ws + c.p.sh,
+                    c.s);
 }
 
 // F[:, :C] holds the block input; writes the RDB output to b.r
@@ -704,29 +750,8 @@ dn_status wgrad_g(const Ctx& c, float* dprm, int mode, const IConv& L, const Vie
     set_error("ImprovedUNet: bias does not follow its weight");
     return DN_ERR_ARG;
   }
-  if (!gwgrad_ok(mode, L.cin, L.cout, g, x)) {
-    set_error("ImprovedUNet: no weight-gradient kernel for this layer shape");
-    return DN_ERR_ARG;
-  }
-  float* slab = c.ws + c.p.slab;
-  const long n = (long)L.cout * L.cin * taps + (bias ? L.cout : 0);
-  WgradArgs a{};
-  a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
-  a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
-  a.N = c.p.N; a.KH = h; a.KW = w; a.Cout = L.cout; a.Cin = L.cin;
-  a.zeros = slab; a.slab = slab + 64; a.slab_stride = n;
-  a.wlayout = 0; a.cin_total = L.cin; a.ci_base = 0; a.bias = bias ? 1 : 0;
-  int sp = gwgrad_splits(mode, c.p.N, h, w, L.cin, L.cout);
-  IU_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s2));
-  // fp32_x6: the 3x3 weight gradients on the bf16x6 kernel too
-  if (c.prec == DN_PREC_FP32_X6 && mode == W_C3 && gwgrad_x6_ok(a)) {
-    sp = gwgrad_x6_splits(a, sp);
-    IU_TRY(launch_gwgrad_x6(a, sp, s2));
-  } else {
-    IU_TRY(launch_gwgrad(mode, a, sp, s2));
-  }
-  IU_TRY(launch_reduce(slab + 64, n, sp, n, dprm + L.w, s2));
-  return DN_OK;
+  return gwgrad_run(mode, g, x, c.p.N, h, w, L.cin, L.cout, bias, c.prec, dprm + L.w,
+                    c.ws + c.p.slab, s2);
 }
 
 // dx (first nout input channels) = conv^T(g) with epilogue epi (aux = mask / residual)
@@ -764,16 +789,9 @@ dn_status gn_bwd(const Ctx& c, float* dprm, const IGN& g, const View& dy, const 
                  int w, const float* stats, const View& dz) {
   if (c.dry) return DN_OK;
   OpScope prof(c.s, "gnbwd", g.C, 1, 1, h, w, c.p.N, 0.0);
-  const int N = c.p.N;
-  const long P = (long)h * w;
-  const int S = chan_sums_splits(N, P);
-  double* part = reinterpret_cast<double*>(c.ws + c.p.gpart);
-  IU_TRY(launch_chan_sums(dy, &z, N, P, g.C, S, part, c.s));
-  IU_TRY(launch_gn_bwd_fin(part, S, N, g.C, g.G, P, c.prm + g.g, stats, c.ws + c.p.ca,
-                           c.ws + c.p.cb, c.ws + c.p.ccf, dprm + g.g, dprm + g.b, c.s));
-  IU_TRY(launch_affine(dy, &z, c.ws + c.p.ca, c.ws + c.p.cb, c.ws + c.p.ccf, 0, nullptr, dz, N, P,
-                       g.C, c.s));
-  return DN_OK;
+  return gn_backward(dy, z, c.p.N, (long)h * w, g.C, g.G, c.prm + g.g, stats, dz, dprm + g.g,
+                     dprm + g.b, reinterpret_cast<double*>(c.ws + c.p.gpart), c.ws + c.p.ca,
+                     c.ws + c.p.cb, c.ws + c.p.ccf, c.s);
 }
 
 // ResBlock backward: dout -> b.dr (gradient of the block input r)

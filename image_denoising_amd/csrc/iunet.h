@@ -60,6 +60,28 @@ struct IPlan {
   long total_floats = 0;
 };
 
+// ---- launch sequences the executor shares with the op-level entry points (capi.cpp) --------
+// GroupNorm(G groups of C channels, eps 1e-5) over N x P pixels of NHWC views.  part holds
+// gn_part_doubles(N, P, C) doubles, every coefficient array N * C floats (16-byte aligned).
+// Forward: stats [N][G] (mean, rstd) saved, y = [res +] [leaky](z * scale + shift).
+long gn_part_doubles(int N, long P, int C);
+dn_status gn_forward(const View& z, int N, long P, int C, int G, const float* gamma,
+                     const float* beta, int act, const View* res, const View& y, float* stats,
+                     double* part, float* scale, float* shift, hipStream_t s);
+// Backward of the normalisation alone (dy = the gradient of z * scale + shift): dz, and dgamma /
+// dbeta [C] overwritten.
+dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G,
+                      const float* gamma, const float* stats, const View& dz, float* dgamma,
+                      float* dbeta, double* part, float* ca, float* cb, float* cc, hipStream_t s);
+// The blocked weight gradient (mode W_C3 / W_C1, any Cout in output-channel blocks over
+// blockIdx.z, views with a channel offset): dwb = [W (cout, cin, k, k) | b (cout) if bias] from
+// g = dL/d(conv output) and the conv's input x.  slab: 64 floats (zeroed here, the kernels' padding
+// source) followed by gwgrad_slab_floats(); prec DN_PREC_FP32_X6 takes the bf16x6 kernels where
+// gwgrad_x6_ok.
+long gwgrad_slab_floats(int mode, int N, int h, int w, int cin, int cout);
+dn_status gwgrad_run(int mode, const View& g, const View& x, int N, int h, int w, int cin,
+                     int cout, bool bias, int prec, float* dwb, float* slab, hipStream_t s);
+
 bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err);
 bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan& p,
                       std::string& err);

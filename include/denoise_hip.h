@@ -425,8 +425,10 @@ dn_status dn_iunet_backward(const dn_unet_cfg* cfg, const float* params, const f
                             float* dparams, int N, int H, int W, void* ws, size_t ws_bytes,
                             void* stream);
 /* dn_iunet_forward / dn_iunet_backward with the 3x3 convolutions' arithmetic chosen by
-   precision: DN_PREC_FP32 or DN_PREC_FP32_X6 (forward and data gradient as exact split-bf16
-   products; weight gradients, 1x1 convs and the noise estimator stay on the fp32 kernels). */
+   precision: DN_PREC_FP32 or DN_PREC_FP32_X6 (the 3x3 convs' forward, data gradient and weight
+   gradient as exact split-bf16 products where the bf16x6 kernels have a tile for the shape -- the
+   weight gradient from 8-pixel-wide levels up, see dn_conv2d_backward_weight_blocked; 1x1 convs,
+   the level-0 conv and the noise estimator stay on the fp32 kernels). */
 dn_status dn_iunet_forward_prec(const dn_unet_cfg* cfg, const float* params, const float* x,
                                 float* y, int N, int H, int W, void* ws, size_t ws_bytes,
                                 int precision, void* stream);
@@ -438,6 +440,40 @@ dn_status dn_iunet_backward_prec(const dn_unet_cfg* cfg, const float* params, co
    xb cf */
 dn_status dn_iunet_debug_buffers(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
                                  int64_t* desc, int max_entries, int* n_entries);
+
+/* ---- ImprovedUNet building blocks as ops (the launch sequences the executor runs, for tests) --
+   Every activation operand is an NHWC view: element (pixel, c) at ptr[pixel * stride + off + c],
+   stride and off multiples of 4 floats, ptr 16-byte aligned, off + C <= stride. */
+/* GroupNorm(G, C) with eps 1e-5 (norm2d('gn'), arch_unet.py:7-15, in ResBlock :422-433) over
+   N x H x W pixels; C a multiple of 4 and of G, C <= 1024.  scratch holds
+   dn_groupnorm_scratch_size() bytes (16-byte aligned).
+   Forward: y = [res +] [LeakyReLU(0.2) if act](gamma * (z - mean) * rstd + beta); res nullable;
+   stats [N][G][2] receives (mean, rstd) per image and group for the backward. */
+size_t dn_groupnorm_scratch_size(int N, int H, int W, int C);
+dn_status dn_groupnorm_forward(const float* z, int z_stride, int z_off, const float* res,
+                               int res_stride, int res_off, float* y, int y_stride, int y_off,
+                               int N, int H, int W, int C, int G, const float* gamma,
+                               const float* beta, int act, float* stats, void* scratch,
+                               size_t scratch_bytes, void* stream);
+/* Backward of the normalisation itself: dy = dL/d(gamma * (z - mean) * rstd + beta) (a caller
+   applies LeakyReLU' first; the residual's gradient is dy unchanged), z and stats as the forward
+   saw / saved them.  Writes dz and overwrites dgamma [C], dbeta [C]; deterministic. */
+dn_status dn_groupnorm_backward(const float* dy, int dy_stride, int dy_off, const float* z,
+                                int z_stride, int z_off, float* dz, int dz_stride, int dz_off,
+                                int N, int H, int W, int C, int G, const float* gamma,
+                                const float* stats, float* dgamma, float* dbeta, void* scratch,
+                                size_t scratch_bytes, void* stream);
+/* The ImprovedUNet executor's weight gradient: any Cout in output-channel blocks of 96 / 48 / 32
+   in one launch, 3x3/pad1 (Cin >= 16) or 1x1.  g = dL/d(conv output) [N,H,W] x Cout and the conv's
+   input x [N,H,W] x Cin; dwb = dw [Cout,Cin,k,k] followed by db [Cout] when bias != 0.  precision
+   DN_PREC_FP32, or DN_PREC_FP32_X6: 3x3 layers at W >= 8 on the bf16x6 kernels, every other shape
+   on the fp32 kernels.  slab holds dn_conv2d_wgrad_blocked_slab_size() bytes, what the
+   ImprovedUNet workspace plan reserves for that layer. */
+size_t dn_conv2d_wgrad_blocked_slab_size(int N, int H, int W, int Cin, int Cout, int ksize);
+dn_status dn_conv2d_backward_weight_blocked(const float* g, int g_stride, int g_off,
+                                            const float* x, int x_stride, int x_off, int N, int H,
+                                            int W, int Cin, int Cout, int ksize, int bias,
+                                            int precision, float* dwb, void* slab, void* stream);
 
 #ifdef __cplusplus
 }

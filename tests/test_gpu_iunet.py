@@ -222,7 +222,7 @@ def test_n2n_step_with_improved_unet_vs_oracle(prec):
     assert rel_err(tr.grad.cpu().numpy(), p.grad.numpy()) < GRAD_TOL
 
 
-def _device_leaky_masks(net, ws, x, C):
+def _device_leaky_masks(net, ws, x, C, tr=None):
     """The LeakyReLU decisions the device took in its last forward on ws (its saved
     activations, dn_iunet_debug_buffers), in the order of the oracle's leaky_relu calls:
     noise_estimator.0; per down level: downs.i.0, 4 RDB growth convs, ResBlock a1; bottle: 4
@@ -234,9 +234,10 @@ def _device_leaky_masks(net, ws, x, C):
     n = ctypes.c_int()
     _lib.call("dn_iunet_debug_buffers", ctypes.byref(net._cfg), N, H, W, 1, desc, 64,
               ctypes.byref(n))
-    tr = []
-    with torch.no_grad():
-        iunet_ref.forward(net.flat_params.cpu().double(), x.double(), C, C, trace=tr)
+    if tr is None:  # (name, tensor) of every traced activation: only names and shapes are used
+        tr = []
+        with torch.no_grad():
+            iunet_ref.forward(net.flat_params.cpu().double(), x.double(), C, C, trace=tr)
     fws = ws.view(torch.float32)
     dev = {}
     for i, (name, ref) in enumerate(tr):
@@ -319,5 +320,106 @@ def test_x6_grads_as_accurate_as_fp32_vs_fp64(golden, C, monkeypatch):
     print(f"\nC={C} y: fp32 {e32:.2e} x6 {e6:.2e}; grad max: fp32 {p32.max():.2e} x6 "
           f"{p6.max():.2e}; median: fp32 {np.median(p32):.2e} x6 {np.median(p6):.2e}")
     assert e6 < FP32_TOL and e6 < 4 * e32 + 1e-7, (e6, e32)
+    assert p6.max() < 4 * p32.max() + 1e-7, (p6.max(), p32.max())
+    assert np.median(p6) < 4 * np.median(p32) + 1e-7, (np.median(p6), np.median(p32))
+
+
+def _profiled_step(net, x, dy, ws, tr=None):
+    """forward + backward on ws under the launch profiler -> (y, flat gradient, launch records,
+    the device's LeakyReLU decisions when given the oracle's trace `tr`)"""
+    from image_denoising_amd import _lib
+
+    N, C, H, W = x.shape
+    y = torch.empty(x.shape, device=DEV)
+    grad = torch.empty_like(net.flat_params)
+    _lib.profile_ops(True)
+    try:
+        net._run_forward(x.to(DEV), y, ws)
+        masks = _device_leaky_masks(net, ws, x, C, tr) if tr is not None else None
+        net._run_backward(dy.to(DEV), grad, ws, N, H, W)
+        recs = _lib.profile_ops_take()
+    finally:
+        _lib.profile_ops(False)
+    return y, grad, recs, masks
+
+
+@pytest.mark.parametrize("shape,seed", [((1, 1, 32, 128), 3), ((2, 3, 32, 128), 17)])
+def test_wide_levels_take_x6_weight_gradient_vs_fp64(shape, seed, monkeypatch):
+    """128 pixels is the smallest width at which the bottleneck (8 wide: k_wgrad3p<3,96>) and
+    level 3 (16 wide: k_wgrad3p<4,96>) take the blocked bf16x6 weight gradient, in 2 / 4 / 8
+    output-channel blocks for the 192 / 384 / 768-output layers, and their growth convs
+    (Cin = 192 .. 480) the 32-wide split kernels.  What ran is asserted from the launch records;
+    y and all 174 parameter gradients are compared per tensor with the fp64 oracle under the
+    device's own LeakyReLU decisions, the bf16x6 errors held to the size of the fp32 kernels'."""
+    N, C, H, W = shape
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.rand(shape, generator=gen)
+    assert _pool_gap(x, C) >= 1e-5
+    dy = torch.randn(shape, generator=gen)
+    net = _net(C).to(DEV)
+    table = iunet_ref.layer_table(C, C)
+    assert len(table) == 174
+    wide = [i for i, (_, sh) in enumerate(table) if len(sh) == 4 and sh[0] in (192, 384, 768)]
+    monkeypatch.delenv("DN_WG_SLAB_SCALAR", raising=False)
+    tr = []  # the oracle's traced activations: their names and shapes locate the device's
+    with torch.no_grad():
+        iunet_ref.forward(net.flat_params.cpu(), x, C, C, trace=tr)
+    errs, refs = {}, []
+    for prec in PRECS:
+        net.set_precision(prec)
+        ws = net._workspace(N, H, W, with_backward=True, fresh=True)
+        y, grad, recs, masks = _profiled_step(net, x, dy, ws, tr)
+        wg = [r for r in recs if r["op"] == "wgrad3"]
+        w96 = [r for r in wg if r["NOUT"] in (192, 384, 768)]
+        w32 = [r for r in wg if r["NOUT"] == 32 and r["W"] <= W >> 3]
+        assert {r["NOUT"] for r in w96} == {192, 384, 768} and len(w32) == 4 * 3, (w96, w32)
+        if prec == "fp32_x6":
+            for r in w96:  # 16-pixel stages from 16-wide rows up, 8-pixel ones at the bottleneck
+                want = "k_wgrad3p<3,96>" if r["W"] < 16 else "k_wgrad3p<4,96>"
+                assert r["kernel"] == want, r
+            assert {r["kernel"] for r in w96 if r["NOUT"] == 768} == {"k_wgrad3p<3,96>"}
+            assert {"k_wgrad3p<3,96>", "k_wgrad3p<4,96>"} <= {r["kernel"] for r in w96 if r["NOUT"] == 384}
+            assert all(r["kernel"].startswith("k_wgrad3s<2,1,") for r in w32), w32
+            assert max(r["K"] for r in w32) == 480 and min(r["K"] for r in w32) == 192, w32
+        else:
+            bad = [r for r in recs if r["kernel"].startswith(("k_wgrad3p", "k_wgrad3s", "k_wgrad3q"))]
+            assert not bad, bad
+        # the fp64 oracle under this run's LeakyReLU decisions (one reference when both agree)
+        ref = next((r for m, r in refs if all(torch.equal(a, b) for a, b in zip(m, masks))), None)
+        if ref is None:
+            mf = _MaskedF(masks)
+            monkeypatch.setattr(iunet_ref, "F", mf)
+            p = net.flat_params.cpu().double().requires_grad_(True)
+            y64 = iunet_ref.forward(p, x.double(), C, C)
+            y64.backward(dy.double())
+            monkeypatch.undo()
+            assert not mf.masks
+            ref = (y64.detach().numpy(), p.grad.numpy())
+            refs.append((masks, ref))
+        gr = grad.cpu().numpy()
+        off, per = 0, []
+        for _, sh in table:
+            k = int(np.prod(sh))
+            per.append(rel_err(gr[off:off + k], ref[1][off:off + k]))
+            off += k
+        assert off == gr.size
+        errs[prec] = (rel_err(y.cpu().numpy(), ref[0]), np.array(per))
+        if prec == "fp32_x6":
+            # dword slab stores instead of the staged float4 rows: the same bits
+            monkeypatch.setenv("DN_WG_SLAB_SCALAR", "1")
+            _, grad_sc, recs_sc, _ = _profiled_step(net, x, dy, ws)
+            monkeypatch.delenv("DN_WG_SLAB_SCALAR")
+            k_sc = [r["kernel"] for r in recs_sc if r["kernel"].startswith("k_wgrad3p")]
+            assert len(k_sc) >= len(w96) and all(k.endswith(" dword") for k in k_sc), k_sc
+            assert torch.equal(grad.view(torch.int32), grad_sc.view(torch.int32))
+    (e32, p32), (e6, p6) = errs["fp32"], errs["fp32_x6"]
+    print(f"\n{shape} y: fp32 {e32:.2e} x6 {e6:.2e}; grad max: fp32 {p32.max():.2e} x6 "
+          f"{p6.max():.2e}; median: fp32 {np.median(p32):.2e} x6 {np.median(p6):.2e}")
+    for i in wide:
+        print(f"  {table[i][0]} {tuple(table[i][1])}: fp32 {p32[i]:.2e} x6 {p6[i]:.2e}")
+    assert e32 < FP32_TOL and e6 < FP32_TOL and e6 < 4 * e32 + 1e-7, (e6, e32)
+    bad = [(table[i][0], p32[i], p6[i]) for i in range(len(table))
+           if p32[i] > GRAD_TOL or p6[i] > GRAD_TOL]
+    assert not bad, bad[:8]
     assert p6.max() < 4 * p32.max() + 1e-7, (p6.max(), p32.max())
     assert np.median(p6) < 4 * np.median(p32) + 1e-7, (np.median(p6), np.median(p32))

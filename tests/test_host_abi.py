@@ -152,6 +152,30 @@ def test_multistep_lr_matches_torch_scheduler():
             sch.step()
 
 
+def test_blocked_wgrad_slab_and_groupnorm_scratch_sizes():
+    """dn_conv2d_wgrad_blocked_slab_size: 64 zero floats + whole [W ; b] rows (one per split), one
+    row where the level has too few pixels to split, never past the 256 MB cap, 0 for a kernel
+    size the op does not have.  dn_groupnorm_scratch_size: the fp64 partial sums of every
+    (image, pixel split, channel) and three per-(image, channel) coefficient arrays."""
+    from image_denoising_amd import _lib
+
+    lib = _lib.lib()
+    for cin, cout, k, N, H, W in [(192, 192, 3, 2, 5, 9), (384, 768, 3, 1, 4, 8),
+                                  (480, 32, 3, 2, 5, 9), (512, 384, 1, 2, 2, 8),
+                                  (384, 384, 3, 64, 8, 8), (24, 24, 3, 64, 128, 128)]:
+        row = cout * cin * k * k + cout
+        b = lib.dn_conv2d_wgrad_blocked_slab_size(N, H, W, cin, cout, k)
+        assert b % 4 == 0 and b >= 4 * (64 + row) and (b // 4 - 64) % row == 0, (cin, cout, b)
+        assert b <= 4 * ((64 << 20) + 64)
+        assert lib.dn_conv2d_wgrad_blocked_slab_size(4 * N, H, W, cin, cout, k) >= b
+    assert lib.dn_conv2d_wgrad_blocked_slab_size(1, 4, 8, 384, 768, 3) == 4 * (64 + 384 * 768 * 9 + 768)
+    assert lib.dn_conv2d_wgrad_blocked_slab_size(1, 4, 8, 384, 768, 2) == 0
+    # 23 x 23 pixels, one image: 529 // 256 = 2 pixel splits
+    assert lib.dn_groupnorm_scratch_size(1, 23, 23, 48) >= 8 * 2 * 2 * 48 + 4 * 3 * 48
+    assert lib.dn_groupnorm_scratch_size(130, 4, 4, 384) >= 8 * 2 * 130 * 384 + 4 * 3 * 130 * 384
+    assert lib.dn_groupnorm_scratch_size(1, 4, 4, 6) == 0  # C must be a multiple of 4
+
+
 def test_wgrad_slab_size_is_bounded():
     from image_denoising_amd import _lib
 
