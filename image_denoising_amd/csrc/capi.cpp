@@ -630,7 +630,7 @@ dn_status dn_conv2d_backward_data_x6(const float* dz, int N, int H, int W, int C
     a.x6_tail = tail;
     a.zc = zc;
     a.wp = static_cast<const float*>(pack_ws);
-    a.wp_z = zc ? x6_pack_elems(Cout, Cin, zc) / ((Cin + zc - 1) / zc) : 0;
+    a.wp_z = x6_wp_z(Cout, Cin, zc);
     a.epi = mask ? EPI_MASK : (accumulate ? EPI_ACCUM : EPI_PLAIN);
     set_mask(a, View{const_cast<float*>(mask), mask_stride, 0});
     const OpTimer timer(s, "dgrad3", 2.0 * Cout * Cin * 9 * N * H * W, Cout, Cin, H, W, N);

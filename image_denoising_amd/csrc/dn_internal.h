@@ -431,6 +431,10 @@ long bf16_pack_elems(int K, int nout, int ksize = 3);
 long bf16_stage_elems(int nout, int ksize);  // bf16 per weight stage of the image (-1: no tile)
 // ---- fp32 3x3 conv on the bf16 matrix cores by three-way operand splitting (conv_x6.hip) ----
 long x6_pack_elems(int K, int nout, int zc);  // bf16 elements of a pre-split weight image
+// bf16 elements of one output-channel block of a z-blocked image (FwdArgs::wp_z; zc == 0: 0)
+inline long x6_wp_z(int K, int nout, int zc) {
+  return zc ? x6_pack_elems(K, nout, zc) / ((nout + zc - 1) / zc) : 0;
+}
 hipError_t launch_pack_x6(const WView& wv, int K, int nout, int zc, void* out, hipStream_t s,
                           int tail = 0);
 // packing of a partial last 32-channel chunk for the pipelined kernel: 1 = <= 4 channels,

@@ -163,7 +163,7 @@ hipError_t x6run(const View& in, int N, int H, int W, int K, const float* wp, in
   FwdArgs a = fwd_args(in, N, H, W, K, nout, out, layout);
   a.x6_tail = tail;
   a.zc = x6_zc(nout);
-  a.wp = wp; a.wp_z = a.zc ? x6_pack_elems(K, nout, a.zc) / ((nout + a.zc - 1) / a.zc) : 0;
+  a.wp = wp; a.wp_z = x6_wp_z(K, nout, a.zc);
   a.bias = bias; a.epi = epi;
   set_mask(a, aux);
   return launch_fwd_x6(a, s);

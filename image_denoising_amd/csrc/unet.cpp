@@ -364,11 +364,12 @@ hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const flo
 
 hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
                  float* dwb, float* slab, int splits, hipStream_t s, bool x6, const float* zeros,
-                 RedBatch* rb, int head_gnb, const float* hd_dy, int hd_dy_stride,
-                 const float* hd_wc, float* hd_slab_c, float* hd_dwc) {
+                 RedBatch* rb, const WgradHead* head) {
   WgradArgs a{};
-  a.head_gnb = head_gnb; a.hd_dy = hd_dy; a.hd_dy_stride = hd_dy_stride; a.hd_wc = hd_wc;
-  a.hd_slab_c = hd_slab_c; a.hd_dwc = hd_dwc;
+  if (head) {
+    a.head_gnb = head->gnb; a.hd_dy = head->dy; a.hd_dy_stride = head->dy_stride;
+    a.hd_wc = head->wc; a.hd_slab_c = head->slab_c; a.hd_dwc = head->dwc;
+  }
   a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
   a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
   a.N = N; a.KH = KH; a.KW = KW; a.Cout = cout; a.Cin = cin;
@@ -396,326 +397,384 @@ hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, 
 // ------------------------------------------------------------------------------------
 // forward: arch_unet.py:194-260 (non-blind-spot branch)
 // ------------------------------------------------------------------------------------
-dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y, float* ws,
-                       hipStream_t s, int prec, const uint8_t* sel_rd, int pack) {
-  const StreamDeviceGuard device_guard(s);
+// A pass decides once, in fwd_routes(), which kernel every layer takes and which weight image in
+// the workspace that kernel reads; pack_forward() writes exactly those images and run_forward()
+// launches on them, each by a switch on the route's kind.
+namespace {
+
+enum FwdKind {
+  F_F32,        // conv on the fp32 kernel (3x3 or 1x1; Plan::packF)
+  F_X6,         // 3x3 conv on the bf16x6 kernels: split fp32 operands on the bf16 matrix cores
+  F_BF16,       // conv on the bf16 kernel: bf16 operands, fp32 accumulation / bias / activation
+  F_UP_F32,     // ConvTranspose2d(2,2) on the fp32 kernel
+  F_UP_X6,      // ... on the persistent bf16x6 kernel (k_deconv_x6; `plain`: plain bf16 products)
+  F_UP_BF16,    // ... as a bf16 1x1 launch per output parity
+  F_FUSED_UP1,  // up1 and dec_conv1a: ONE composed image and launch (k_upconv3_x6)
+  F_HEAD,       // nin_a .. nin_c inside the head launch, on the head's image
+};
+struct FwdRoute {
+  int kind;
+  long img;    // workspace offset (floats) of the layer's weight image
+  int tail;    // F_X6: x6_image_mode (tail packing of the last K chunk | X6_W6) | X6_T1
+  bool plain;  // F_UP_X6 in the bf16 base
+  bool in_bf16, out_bf16;  // F_BF16: the input / output activation stored as bf16
+  bool pool;   // enc_conv1..5: the 2x2 max-pool fused into the conv's epilogue
+};
+enum HeadKind {
+  H_F32,       // dec_conv1b + nin_a + nin_b + nin_c in one fp32 kernel (launch_head)
+  H_NIN,       // bf16x6 dec_conv1b, then the fp32 nin head (out_nc above X6_HEAD_OCMAX)
+  H_NIN_X6,    // bf16x6 dec_conv1b (or the pair-pixel pass), then k_nin_head_x6
+  H_NIN_BF16,  // bf16 dec_conv1b, then k_nin_head_x6 in plain bf16 products
+  H_BF16_3,    // bf16 dec_conv1b, nin_a and nin_b as bf16 1x1 launches, nin_c on the fp32 kernel
+};
+struct FwdRoutes {
+  FwdRoute r[NL];  // ENC1 .. NINC
+  int head;
+  long head_img;   // the head's nin_a | nin_b images (not H_BF16_3)
+  bool up1_fuse;
+  bool sel;        // dec_conv1b and the head on the N2N pair pixels only
+  bool w6_sel;     // ... dec_conv1b on k_c3w6s: cell lists and the tap-transposed image img_xv
+  long img_xv;
+  bool enc0_c1;    // enc_conv0 copies x into its slice of the up1 concat buffer
+  bool enc0_bf16;  // enc_conv0's output stored as bf16
+  int pool_only;   // a conv with a fused pool stores only the pooled output
+};
+
+FwdRoutes fwd_routes(const Plan& p, int prec, bool pair_pass) {
   const bool bf16 = prec == DN_PREC_BF16, x6 = prec == DN_PREC_FP32_X6;
-  // (bf16x6 96-channel deconvs: k_deconv_x6)
+  // the encoder's 2x2 max-pools fused into the convs' epilogues (DN_POOL_FUSE=0: separate
+  // k_pool_fwd launches, A/B)
+  static const bool pool_fuse = !getenv("DN_POOL_FUSE") || atoi(getenv("DN_POOL_FUSE")) != 0;
+  // DN_UP1_FUSE=0: up1 and dec_conv1a as two launches (A/B)
+  static const bool up1_fuse_env = !getenv("DN_UP1_FUSE") || atoi(getenv("DN_UP1_FUSE")) != 0;
+  FwdRoutes R{};
+  // bf16 base (forward-only plans): bf16 storage of the activations that only a bf16 conv reads
+  // (enc_conv0 -> enc_conv1, dec_conv{l}a -> dec_conv{l}b).  The consumer rounds its staged
+  // operands to bf16 anyway, so the result is bit-identical and those tensors move half the bytes
+  const bool bf16_store = bf16 && !p.with_bwd;
+  for (int i = ENC1; i <= NINC; ++i) {
+    const Layer& L = p.P.L[i];
+    FwdRoute& r = R.r[i];
+    if (L.deconv) {
+      // the 96-channel deconvs on the persistent bf16x6 kernel, also in the bf16 base (one pass
+      // over the input instead of a bf16 1x1 launch per output parity)
+      if ((x6 || bf16) && p.packUX[i] >= 0) { r.kind = F_UP_X6; r.img = p.packUX[i]; r.plain = bf16; }
+      else if (bf16 && p.packBF[i] >= 0) { r.kind = F_UP_BF16; r.img = p.packBF[i]; }
+      else { r.kind = F_UP_F32; r.img = p.packF[i]; }
+    } else if (x6 && p.packX[i] >= 0) {
+      r.kind = F_X6; r.img = p.packX[i];
+      // the pipelined kernel takes a partial last K chunk (dec_conv1a's x channels, the
+      // 48-channel encoder's second chunk) packed over fewer stages; | X6_W6: the Winograd kernel
+      // on the 96- and 48-output layers from one round of 8 x 16 tiles.  dec_conv1a reads
+      // [up1 | x | zero pad] (c1kp = c1k rounded to 4): taking the zero pad channel as a reduction
+      // channel (its packed weights are zero) keeps K % 4 == 0 (pipelined)
+      const int l = layer_level(i);
+      r.tail = x6_image_mode(p.N, p.H >> l, p.W >> l, i == D1A ? p.c1kp : L.cin, L.cout, 0, true);
+      // dec_conv1a at C = 1 on the Winograd kernel: the image channel alone in the last chunk
+      if (i == D1A && (r.tail & X6_W6) && (r.tail & 7) == 1 && L.cin % 32 == 1 && L.cout == 96)
+        r.tail |= X6_T1;
+    } else if (bf16 && p.packBF[i] >= 0) {
+      r.kind = F_BF16; r.img = p.packBF[i];
+      r.in_bf16 = bf16_store && (i == ENC1 || i == D1B || i == D2B || i == D3B || i == D4B || i == D5B);
+      r.out_bf16 = bf16_store && (i == D1A || i == D2A || i == D3A || i == D4A || i == D5A);
+    } else {
+      r.kind = F_F32; r.img = p.packF[i];
+    }
+    r.pool = pool_fuse && i >= ENC1 && i <= ENC5 && (r.kind == F_X6 || r.kind == F_BF16);
+  }
+  R.enc0_bf16 = bf16_store;  // only enc_conv1 reads enc_conv0's output in a forward-only plan
+  // forward-only plans: an encoder conv whose pool is fused stores only the pooled output (its
+  // full-resolution activation is read by nothing but that pool; the backward's pool routing
+  // reads it in plans with a backward)
+  R.pool_only = !p.with_bwd ? 1 : 0;
+  // Forward-only bf16x6 plans from the grid size k_c3w6 takes dec_conv1a at: up1 and dec_conv1a
+  // as ONE launch (k_upconv3_x6: the deconv composed into the conv's 96 up1 channels, 2x2 taps
+  // per output parity over d2b; nothing else reads up1 without a backward)
+  const int d1a_tail = R.r[D1A].tail;
+  R.up1_fuse = up1_fuse_env && x6 && !p.with_bwd && p.packUC >= 0 && p.nf == 48 && p.C <= 4 &&
+               (d1a_tail & X6_W6);
+  if (R.up1_fuse) {
+    R.r[UP1] = FwdRoute{F_FUSED_UP1, p.packUC};
+    R.r[D1A] = FwdRoute{F_FUSED_UP1, p.packUC};
+  }
+  // dec_conv1a reading x itself (X6_T1, the fused launch): the concat slice is never read -- 16
+  // scattered bytes per 512-B pixel cost the enc_conv0 launch 0.19 ms/step; c1's channels
+  // [2nf, c1s) then hold stale data, which the debug-buffer contract in denoise_hip.h states
+  R.enc0_c1 = !(x6 && ((d1a_tail & X6_T1) || R.up1_fuse));
+  // the head.  bf16 base (inference only): the fused head kernel in plain bf16 products instead
+  // of nin_a / nin_b as two bf16 1x1 launches + an fp32 nin_c (two 96-channel round trips through
+  // HBM saved); it reads d1b as bf16
+  if (bf16) R.head = !p.with_bwd && p.OC <= X6_HEAD_OCMAX ? H_NIN_BF16 : H_BF16_3;
+  else if (x6) R.head = p.OC <= X6_HEAD_OCMAX ? H_NIN_X6 : H_NIN;
+  else R.head = H_F32;
+  R.head_img = p.packH;
+  if (R.head != H_BF16_3)
+    for (int i = NINA; i <= NINC; ++i) R.r[i] = FwdRoute{F_HEAD, p.packH};
+  if (R.head == H_NIN_BF16) R.r[D1B].out_bf16 = true;
+  // the N2N no-grad pass: the bf16x6 nin head at the pair pixels; its dec_conv1b on the Winograd
+  // kernel k_c3w6s wherever the full forward's dec_conv1b has a Winograd image, the direct
+  // k_c3x6s below one round of tiles
+  R.sel = x6 && pair_pass && !p.with_bwd && p.OC <= X6_HEAD_OCMAX;
+  R.w6_sel = R.sel && p.packXV >= 0 && (R.r[D1B].tail & X6_W6);
+  R.img_xv = p.packXV;
+  return R;
+}
+
+// every weight image of the pass (fp32, bf16x6 and bf16 alike) in one pack launch
+dn_status pack_forward(const Plan& p, const FwdRoutes& R, const float* prm, float* ws,
+                       hipStream_t s) {
+  auto Bs = [&](int i) { return prm + p.P.L[i].woff + p.P.L[i].wcount; };
+  PackBatch pb;
+  auto add = [&](bool ok, const PackJob& j) { return ok ? pack_add(pb, j, s) : hipErrorInvalidValue; };
+  for (int i = ENC1; i <= NINC; ++i) {
+    const Layer& L = p.P.L[i];
+    const FwdRoute& r = R.r[i];
+    const float* w = prm + L.woff;
+    PackJob j;
+    switch (r.kind) {
+      case F_FUSED_UP1:  // one composed image for the pair
+        if (i == D1A)
+          DN_TRY(add(true, pack_job_upconv_x6(w, Bs(D1A), prm + p.P.L[UP1].woff, Bs(UP1), p.C,
+                                              ws + r.img)));
+        break;
+      case F_UP_X6:
+        DN_TRY(add(true, pack_job_deconv_x6(w, ws + r.img)));
+        break;
+      case F_UP_BF16: {  // ConvTranspose2d [cin][cout][2][2]: a 1x1 image per parity
+        const long img = bf16_pack_elems(L.cin, L.cout, 1);
+        for (int ab = 0; ab < 4; ++ab) {
+          WView v{};
+          v.w = w; v.off = ab; v.sK = (long)L.cout * 4; v.sN = 4; v.taps = 1;
+          DN_TRY(add(pack_job_bf16(v, L.cin, L.cout, 1,
+                                   reinterpret_cast<unsigned short*>(ws + r.img) + ab * img, j), j));
+        }
+        break;
+      }
+      case F_UP_F32:
+        DN_TRY(add(pack_job(G_UP, deconv_fwd_view(w, L.cout), L.cin, L.cout, 4, ws + r.img, 0, 0, j), j));
+        break;
+      case F_BF16:
+        if (L.k == 3)
+          DN_TRY(add(pack_job_bf16(conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 3, ws + r.img, j), j));
+        else  // nin_a, nin_b: launches of their own
+          DN_TRY(launch_pack_bf16(conv_fwd_view(w, L.cin, 1), L.cin, L.cout, ws + r.img, s, 1));
+        break;
+      case F_X6:
+        DN_TRY(add(pack_job_x6(conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 0, ws + r.img, r.tail, j), j));
+        break;
+      case F_F32:
+        DN_TRY(add(pack_job(L.k == 3 ? G_C3 : G_C1, conv_fwd_view(w, L.cin, L.k), L.cin, L.cout, 1,
+                            ws + r.img, 0, 0, j), j));
+        break;
+      case F_HEAD:
+        break;
+    }
+    // dec_conv1b's y-tile image for the Winograd pair pass: PK_W6 over the transposed taps
+    if (i == D1B && R.w6_sel) {
+      WView v = conv_fwd_view(w, L.cin, 3);
+      v.flip = 2;
+      DN_TRY(add(pack_job_x6(v, L.cin, L.cout, 0, ws + R.img_xv, X6_W6, j), j));
+    }
+  }
+  const float* wa = prm + p.P.L[NINA].woff;
+  const float* wb = prm + p.P.L[NINB].woff;
+  switch (R.head) {
+    case H_NIN_X6: case H_NIN_BF16:
+      DN_TRY(add(true, pack_job_head_x6(wa, wb, ws + R.head_img)));
+      break;
+    case H_F32: case H_NIN:
+      DN_TRY(launch_pack_head(conv_fwd_view(wa, 96, 1), conv_fwd_view(wb, 96, 1), ws + R.head_img, s, &pb));
+      break;
+    case H_BF16_3:  // the three layers' own images, above
+      break;
+  }
+  DN_TIMED(s, "pack", 0, 0, 0, 0, 0, 0, pack_flush(pb, s));
+  return DN_OK;
+}
+
+dn_status run_forward(const Plan& p, const FwdRoutes& R, const float* prm, const float* x,
+                      float* y, float* ws, hipStream_t s, const uint8_t* sel_rd) {
   const int N = p.N, nf = p.nf, C = p.C;
   auto H = [&](int l) { return p.H >> l; };
   auto Wd = [&](int l) { return p.W >> l; };
   auto Bs = [&](int i) { return prm + p.P.L[i].woff + p.P.L[i].wcount; };
   auto V = [&](long off, int stride, int coff = 0) { return View{ws + off, stride, coff}; };
   const View none{nullptr, 0, 0};
-  // every 3x3 layer (enc_conv1..dec_conv1b): the fp32 kernel, the bf16x6 one (split fp32
-  // operands on the bf16 matrix cores), or the bf16 one (bf16 operands, fp32 accumulation /
-  // bias / activation / storage)
-  // the pipelined split-bf16 kernel takes a partial last K chunk (dec_conv1a's x channels,
-  // the 48-channel encoder's second chunk) packed over fewer stages (x6_tail_mode)
-  // (x6_image_mode: | X6_W6 for the Winograd kernel on the 96- and 48-output layers from one
-  // round of 8 x 16 tiles)
-  // the encoder's 2x2 max-pools fused into the x6 convs' epilogues (DN_POOL_FUSE=0: separate
-  // k_pool_fwd launches, A/B)
-  static const bool pool_fuse = !getenv("DN_POOL_FUSE") || atoi(getenv("DN_POOL_FUSE")) != 0;
-  // (the N2N pair-pixel pass's dec_conv1b runs the Winograd kernel k_c3w6s wherever the full
-  // forward's dec_conv1b has a Winograd image; the direct k_c3x6s below one round of tiles)
-  auto x6_tail_f = [&](int i) -> int {
+  // Conv layer i (enc_conv1 .. nin_b; bias + LeakyReLU, NHWC) at its level, on the kernel and
+  // image of its route.  pool: the 2x2 max-pool of `out` into that view, fused into the conv's
+  // epilogue (bit-identical) or as its own launch
+  auto conv_forward = [&](int i, const View& in, const View& out,
+                          const View* pool = nullptr) -> hipError_t {
     const Layer& L = p.P.L[i];
-    const int l = layer_level(i);
-    const int m = x6_image_mode(N, H(l), Wd(l), i == D1A ? p.c1kp : L.cin, L.cout, 0, true);
-    // dec_conv1a at C = 1 on the Winograd kernel: the image channel alone in the last chunk
-    return m | (i == D1A && (m & X6_W6) && (m & 7) == 1 && L.cin % 32 == 1 && L.cout == 96 ? X6_T1 : 0);
-  };
-  // bf16 base (forward-only plans): bf16 storage of the decoder's a-conv outputs, whose only
-  // reader is the matching b-conv
-  const bool bf16_store = bf16 && !p.with_bwd;
-  // (bf16 base: the fused head kernel in plain bf16 products, see below; it reads d1b as bf16)
-  const bool bf16_head_x6 = bf16 && !p.with_bwd && p.OC <= X6_HEAD_OCMAX;
-  auto bf16_store_out = [&](int i) {
-    if (i == D1B) return bf16_store && bf16_head_x6 && p.packBF[i] >= 0;
-    return bf16_store && (i == D1A || i == D2A || i == D3A || i == D4A || i == D5A) &&
-           p.packBF[i] >= 0 && p.packBF[i + 1] >= 0;
-  };
-  // enc_conv0's output too: only enc_conv1 reads it in a forward-only plan
-  const bool enc0_bf16 = bf16_store && p.packBF[ENC1] >= 0;
-  auto bf16_store_in = [&](int i) {
-    if (i == ENC1) return enc0_bf16;
-    return bf16_store && (i == D1B || i == D2B || i == D3B || i == D4B || i == D5B) &&
-           bf16_store_out(i - 1);
-  };
-  // (dec_conv1b -> the bf16 head: bf16_store_out(D1B))
-  // pool (x6 path, EPI_BIAS_ACT): the 2x2 max-pool of `out` fused into the conv's epilogue into
-  // that view (*pooled set); otherwise the caller pools
-  // forward-only plans: an encoder conv whose pool is fused stores only the pooled output
-  // (its full-resolution activation is read by nothing but that pool; the backward's pool
-  // routing reads it in plans with a backward)
-  const int pool_only = !p.with_bwd ? 1 : 0;
-  // Layer i (enc_conv1 .. nin_c) at its level, on the kernel of the pass's precision: channels,
-  // kernel size, bias and the weight image all come from the layer table and the plan's images
-  auto conv_forward = [&](int i, const View& in, int act, const View& out, int layout,
-                          hipStream_t st, const View* pool = nullptr,
-                          bool* pooled = nullptr) -> hipError_t {
-    if (pooled) *pooled = false;
-    const Layer& L = p.P.L[i];
+    const FwdRoute& r = R.r[i];
     const int l = layer_level(i), h = H(l), w = Wd(l);
-    const OpTimer timer(st, L.k == 3 ? "fwd3" : "fwd1",
-                        2.0 * N * h * w * L.cin * L.cout * L.k * L.k, L.cin, L.cout, h, w, N);
-    const bool on_x6 = x6 && p.packX[i] >= 0, on_bf16 = !on_x6 && bf16 && p.packBF[i] >= 0;
-    if (!on_x6 && !on_bf16)  // the fp32 kernel (dec_conv1a: its c1k real channels)
-      return dn::conv_forward(in, N, h, w, L.cin, ws + p.packF[i], Bs(i), L.cout, L.k, act, out,
-                              layout, st);
-    // dec_conv1a reads [up1 | x | zero pad] (c1kp = c1k rounded to 4): taking the zero pad
-    // channel as a reduction channel (its packed weights are zero) keeps K % 4 == 0 (pipelined)
-    FwdArgs a = fwd_args(in, N, h, w, i == D1A ? p.c1kp : L.cin, L.cout, out, layout);
-    a.bias = Bs(i); a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-    if (on_x6) {
-      a.wp = ws + p.packX[i];
-      a.x6_tail = x6_tail_f(i);  // a partial last K chunk packed over fewer stages
-      if (a.x6_tail & X6_T1) a.in_t1 = x;  // the image channel straight from the network input
-    } else {
-      a.wp = ws + p.packBF[i];
-      // the activations that only a bf16 3x3 conv reads (d_l a -> d_l b, d1a -> d1b) stored as
-      // bf16: the consumer rounds its staged operands to bf16 anyway, so the result is
-      // bit-identical and those tensors move half the bytes
-      a.out_bf16 = bf16_store_out(i);
-      a.in_bf16 = bf16_store_in(i);
-    }
-    // the encoder's pools fused into the 3x3 epilogue
-    if (pool && pool_fuse && act && L.k == 3 && layout == OUT_NHWC && !a.out_bf16) {
-      set_pool(a, *pool, pool_only);
-      if (pooled) *pooled = true;
-    }
-    return on_x6 ? launch_fwd_x6(a, st) : launch_fwd_bf16(a, st, L.k);
-  };
-
-  // the bf16x6 nin head (k_nin_head_x6), also at the pair pixels
-  const bool sel = x6 && sel_rd && !p.with_bwd && p.OC <= X6_HEAD_OCMAX;
-  const bool w6_sel = sel && p.packXV >= 0 && (x6_tail_f(D1B) & X6_W6);
-  const bool head_x6 = x6 && p.OC <= X6_HEAD_OCMAX;
-  // bf16 base (inference only): the fused head kernel in plain bf16 products instead of nin_a /
-  // nin_b as two bf16 1x1 launches + an fp32 nin_c (two 96-channel round trips through HBM
-  // saved; bf16_head_x6 above)
-  // the 96-channel deconvs on the persistent bf16x6 kernel, also in the bf16 base (one pass over
-  // the input instead of a bf16 1x1 launch per output parity)
-  auto deconv_x6_layer = [&](int i) { return (x6 || bf16) && p.packUX[i] >= 0; };
-  // ConvTranspose2d(2,2): fp32 kernel, or the bf16 1x1 kernel per output parity
-  // (layer i's input lives one level below its output)
-  auto deconv_forward = [&](int i, const View& xin, const View& out, hipStream_t st) -> hipError_t {
-    const Layer& L = p.P.L[i];
-    const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
-    const OpTimer timer(st, "deconv", 2.0 * N * h * w * L.cin * L.cout * 4, L.cin, L.cout, h, w, N);
-    const bool on_x6 = deconv_x6_layer(i);
-    if (!on_x6 && !(bf16 && p.packBF[i] >= 0))
-      return dn::deconv_forward(xin, N, h, w, L.cin, ws + p.packF[i], Bs(i), L.cout, out, st);
-    FwdArgs a = fwd_args(xin, N, h, w, L.cin, L.cout, out, OUT_UP2);
-    a.bias = Bs(i); a.epi = EPI_BIAS;
-    if (on_x6) {  // bf16x6 parity GEMMs on the layer's pre-split images
-      if (!deconv_x6_ok(a)) return hipErrorInvalidValue;
-      // (the bf16 base: plain bf16 products, as its convs)
-      return launch_deconv_x6(a, ws + p.packUX[i], st, bf16);
-    }
-    a.wp = ws + p.packBF[i]; a.wp_z = bf16_pack_elems(L.cin, L.cout, 1);
-    return launch_fwd_bf16(a, st, 1);
-  };
-
-  // Forward-only bf16x6 plans from the grid size k_c3w6 takes dec_conv1a at: up1 and dec_conv1a
-  // as ONE launch (k_upconv3_x6: the deconv composed into the conv's 96 up1 channels, 2x2 taps
-  // per output parity over d2b; nothing else reads up1 without a backward).  DN_UP1_FUSE=0: the
-  // two launches (A/B)
-  static const bool up1_fuse_env = !getenv("DN_UP1_FUSE") || atoi(getenv("DN_UP1_FUSE")) != 0;
-  const bool up1_fuse = up1_fuse_env && x6 && !p.with_bwd && p.packUC >= 0 && nf == 48 && C <= 4 &&
-                        (x6_tail_f(D1A) & X6_W6);
-  // every weight image of the pass (fp32, bf16x6 and bf16 alike) in one pack launch (not for a
-  // prepacked forward: dn_unet_pack_weights left them in ws)
-  if (pack != RUN_ONLY) {
-    PackBatch pb;
-    auto add = [&](bool ok, const PackJob& j) { return ok ? pack_add(pb, j, s) : hipErrorInvalidValue; };
-    for (int i = ENC1; i < NINA; ++i) {
-      const Layer& L = p.P.L[i];
-      const float* w = prm + L.woff;
-      PackJob j;
-      if (up1_fuse && (i == UP1 || i == D1A)) {  // one composed image for the pair
-        if (i == D1A)
-          DN_TRY(add(true, pack_job_upconv_x6(w, Bs(D1A), prm + p.P.L[UP1].woff, Bs(UP1), C,
-                                              ws + p.packUC)));
-      } else if (L.deconv && deconv_x6_layer(i)) {
-        DN_TRY(add(true, pack_job_deconv_x6(w, ws + p.packUX[i])));
-      } else if (L.deconv && bf16) {  // ConvTranspose2d [cin][cout][2][2]: a 1x1 image per parity
-        const long img = bf16_pack_elems(L.cin, L.cout, 1);
-        for (int ab = 0; ab < 4; ++ab) {
-          WView v{};
-          v.w = w; v.off = ab; v.sK = (long)L.cout * 4; v.sN = 4; v.taps = 1;
-          DN_TRY(add(pack_job_bf16(v, L.cin, L.cout, 1,
-                                   reinterpret_cast<unsigned short*>(ws + p.packBF[i]) + ab * img, j), j));
+    hipError_t e = hipErrorInvalidValue;
+    {
+      const OpTimer timer(s, L.k == 3 ? "fwd3" : "fwd1",
+                          2.0 * N * h * w * L.cin * L.cout * L.k * L.k, L.cin, L.cout, h, w, N);
+      switch (r.kind) {
+        case F_F32:  // (dec_conv1a: its c1k real channels)
+          e = dn::conv_forward(in, N, h, w, L.cin, ws + r.img, Bs(i), L.cout, L.k, 1, out, OUT_NHWC, s);
+          break;
+        case F_X6: case F_BF16: {
+          FwdArgs a = fwd_args(in, N, h, w, i == D1A ? p.c1kp : L.cin, L.cout, out, OUT_NHWC);
+          a.wp = ws + r.img; a.bias = Bs(i); a.epi = EPI_BIAS_ACT;
+          a.x6_tail = r.tail;
+          if (r.tail & X6_T1) a.in_t1 = x;  // the image channel straight from the network input
+          a.in_bf16 = r.in_bf16; a.out_bf16 = r.out_bf16;
+          if (pool && r.pool) set_pool(a, *pool, R.pool_only);
+          e = r.kind == F_X6 ? launch_fwd_x6(a, s) : launch_fwd_bf16(a, s, L.k);
+          break;
         }
-      } else if (L.deconv) {
-        DN_TRY(add(pack_job(G_UP, deconv_fwd_view(w, L.cout), L.cin, L.cout, 4, ws + p.packF[i], 0, 0, j),
-                   j));
-      } else if (bf16) DN_TRY(add(pack_job_bf16(conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 3,
-                                              ws + p.packBF[i], j), j));
-      else if (x6) DN_TRY(add(pack_job_x6(conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 0,
-                                          ws + p.packX[i], x6_tail_f(i), j), j));
-      else DN_TRY(add(pack_job(L.k == 3 ? G_C3 : G_C1, conv_fwd_view(w, L.cin, L.k), L.cin, L.cout, 1,
-                               ws + p.packF[i], 0, 0, j), j));
-      // dec_conv1b's y-tile image for the Winograd pair pass: PK_W6 over the transposed taps
-      if (i == D1B && w6_sel) {
-        WView v = conv_fwd_view(w, L.cin, 3);
-        v.flip = 2;
-        DN_TRY(add(pack_job_x6(v, L.cin, L.cout, 0, ws + p.packXV, X6_W6, j), j));
+        default:
+          break;
       }
     }
-    if (bf16_head_x6) {
-      DN_TRY(add(true, pack_job_head_x6(prm + p.P.L[NINA].woff, prm + p.P.L[NINB].woff, ws + p.packH)));
-    } else if (bf16) {  // nin_a, nin_b on the bf16 kernel, nin_c (96 -> out_nc) on the fp32 one
-      for (int i = NINA; i <= NINB; ++i)
-        DN_TRY(launch_pack_bf16(conv_fwd_view(prm + p.P.L[i].woff, 96, 1), 96, 96,
-                                ws + p.packBF[i], s, 1));
-      PackJob j;
-      DN_TRY(add(pack_job(G_C1, conv_fwd_view(prm + p.P.L[NINC].woff, 96, 1), 96, p.OC, 1,
-                          ws + p.packF[NINC], 0, 0, j), j));
-    } else if (head_x6) {
-      DN_TRY(add(true, pack_job_head_x6(prm + p.P.L[NINA].woff, prm + p.P.L[NINB].woff, ws + p.packH)));
-    } else {
-      DN_TRY(launch_pack_head(conv_fwd_view(prm + p.P.L[NINA].woff, 96, 1),
-                              conv_fwd_view(prm + p.P.L[NINB].woff, 96, 1), ws + p.packH, s, &pb));
+    if (e != hipSuccess || !pool || r.pool) return e;
+    const OpTimer timer(s, "pool", 0);
+    return launch_pool_fwd(out.p, N, h, w, L.cout, pool->p, pool->stride, pool->off, s);
+  };
+  // ConvTranspose2d(2,2) layer i (its input lives one level below its output)
+  auto deconv_forward = [&](int i, const View& xin, const View& out) -> hipError_t {
+    const Layer& L = p.P.L[i];
+    const FwdRoute& r = R.r[i];
+    const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
+    const OpTimer timer(s, "deconv", 2.0 * N * h * w * L.cin * L.cout * 4, L.cin, L.cout, h, w, N);
+    FwdArgs a = fwd_args(xin, N, h, w, L.cin, L.cout, out, OUT_UP2);
+    a.bias = Bs(i); a.epi = EPI_BIAS;
+    switch (r.kind) {
+      case F_UP_F32:
+        return dn::deconv_forward(xin, N, h, w, L.cin, ws + r.img, Bs(i), L.cout, out, s);
+      case F_UP_X6:  // bf16x6 parity GEMMs on the layer's pre-split images
+        if (!deconv_x6_ok(a)) return hipErrorInvalidValue;
+        return launch_deconv_x6(a, ws + r.img, s, r.plain);
+      case F_UP_BF16:  // the bf16 1x1 kernel per output parity
+        a.wp = ws + r.img; a.wp_z = bf16_pack_elems(L.cin, L.cout, 1);
+        return launch_fwd_bf16(a, s, 1);
+      default:
+        return hipErrorInvalidValue;
     }
-    {
-      const OpTimer timer(s, "pack", 0);
-      DN_TRY(pack_flush(pb, s));
-    }
-  }
-  if (pack == PACK_ONLY) return DN_OK;
+  };
+
   // the pair pass's cell lists first: they depend on the pair choices only, and built here they
   // run beside the other stream's work instead of alone right before the pair pass (~20 us of a
   // step in which nothing else ran, profiles/r6_step_timeline.txt)
-  if (w6_sel)
+  if (R.w6_sel)
     DN_TIMED(s, "sel_lists", 0, 0, 0, 0, 0, 0,
              launch_w6s_lists(sel_rd, N, H(0), Wd(0), reinterpret_cast<unsigned*>(ws + p.w6s_list),
                               reinterpret_cast<int*>(ws + p.w6s_cnt), s));
   // enc_conv0, fused with pool0 = x -> channels [2nf, 2nf+C) of the up1 concat buffer
   DN_TIMED(s, "enc0", 2.0 * N * p.H * p.W * C * nf * 9, C, nf, p.H, p.W, N,
            launch_enc0_fwd(x, N, C, p.H, p.W, prm + p.P.L[ENC0].woff, Bs(ENC0), ws + p.a0,
-                           // (dec_conv1a reading x itself, X6_T1: the concat slice is never read --
-                           // 16 scattered bytes per 512-B pixel cost the launch 0.19 ms/step; c1's
-                           // channels [2nf, c1s) then hold stale data, which the debug-buffer
-                           // contract in denoise_hip.h states)
-                           x6 && ((x6_tail_f(D1A) & X6_T1) || up1_fuse) ? nullptr : ws + p.c1, p.c1s, 2 * nf,
-                           p.c1kp, p.with_bwd ? ws + p.xin : nullptr, s, enc0_bf16));
+                           R.enc0_c1 ? ws + p.c1 : nullptr, p.c1s, 2 * nf, p.c1kp,
+                           p.with_bwd ? ws + p.xin : nullptr, s, R.enc0_bf16));
   {  // enc_conv1 + pool1 -> skip slice of c2
     const View pv = V(p.c[1], p.cs[1], 2 * nf);
-    bool pooled = false;
-    DN_TRY(conv_forward(ENC1, V(p.a0, nf), 1, V(p.a1, nf), OUT_NHWC, s, &pv, &pooled));
-    if (!pooled)
-      DN_TIMED(s, "pool", 0, 0, 0, 0, 0, 0, launch_pool_fwd(ws + p.a1, N, H(0), Wd(0), nf, ws + p.c[1], p.cs[1], 2 * nf, s));
+    DN_TRY(conv_forward(ENC1, V(p.a0, nf), V(p.a1, nf), &pv));
   }
   // enc_conv2..5 + pool2..5 (pool_k -> skip slice of c_{k+1}; pool5 -> p5)
   for (int l = 1; l <= 4; ++l) {
-    const int li = ENC2 + (l - 1);
     const View in = (l == 4) ? V(p.c[4], p.cs[4], nf) : V(p.c[l], p.cs[l], 2 * nf);
     const View pv = l < 4 ? V(p.c[l + 1], p.cs[l + 1], (l + 1 == 4) ? nf : 2 * nf) : V(p.p5, nf, 0);
-    bool pooled = false;
-    DN_TRY(conv_forward(li, in, 1, V(p.a[l], nf), OUT_NHWC, s, &pv, &pooled));
-    if (pooled) continue;
-    DN_TIMED(s, "pool", 0, 0, 0, 0, 0, 0,
-             launch_pool_fwd(ws + p.a[l], N, H(l), Wd(l), nf, pv.p, pv.stride, pv.off, s));
+    DN_TRY(conv_forward(ENC2 + (l - 1), in, V(p.a[l], nf), &pv));
   }
-  DN_TRY(conv_forward(ENC6, V(p.p5, nf), 1, V(p.a6, nf), OUT_NHWC, s));
+  DN_TRY(conv_forward(ENC6, V(p.p5, nf), V(p.a6, nf)));
   // decoder: up5 (a6 -> c5[0:nf]); dec5a/b at level 4
-  DN_TRY(deconv_forward(UP5, V(p.a6, nf), V(p.c[4], p.cs[4], 0), s));
+  DN_TRY(deconv_forward(UP5, V(p.a6, nf), V(p.c[4], p.cs[4], 0)));
   const int up_idx[6] = {0, UP1, UP2, UP3, UP4, UP5};  // up_idx[k]: level k -> level k-1
   const int da_idx[5] = {0, D2A, D3A, D4A, D5A};
   for (int l = 4; l >= 1; --l) {
     if (l < 4)  // up_{l+1}: d_{l+1}b -> c_l[0:2nf]
-      DN_TRY(deconv_forward(up_idx[l + 1], V(p.db[l + 1], 2 * nf), V(p.c[l], p.cs[l], 0), s));
+      DN_TRY(deconv_forward(up_idx[l + 1], V(p.db[l + 1], 2 * nf), V(p.c[l], p.cs[l], 0)));
     const int ia = da_idx[l], ib = da_idx[l] + 1;
     // (dec_conv{l}a reduces over the concat's ck[l] channels == its cin; cs[l] is the stride)
-    DN_TRY(conv_forward(ia, V(p.c[l], p.cs[l]), 1, V(p.da[l], 2 * nf), OUT_NHWC, s));
-    DN_TRY(conv_forward(ib, V(p.da[l], 2 * nf), 1, V(p.db[l], 2 * nf), OUT_NHWC, s));
+    DN_TRY(conv_forward(ia, V(p.c[l], p.cs[l]), V(p.da[l], 2 * nf)));
+    DN_TRY(conv_forward(ib, V(p.da[l], 2 * nf), V(p.db[l], 2 * nf)));
   }
-  // up1: d2b -> c1[0:2nf]
-  if (up1_fuse) {  // (the record carries dec_conv1a's algorithmic FLOPs, as the Winograd launches)
+  // up1: d2b -> c1[0:2nf], then dec_conv1a
+  if (R.up1_fuse) {  // (the record carries dec_conv1a's algorithmic FLOPs, as the Winograd launches)
     FwdArgs a = fwd_args(V(p.db[1], 2 * nf), H(1), Wd(1), N, H(0), Wd(0), p.c1k, 96, V(p.d1a, 96),
                          OUT_NHWC);
-    a.wp = ws + p.packUC; a.in_t1 = x; a.epi = EPI_BIAS_ACT;
+    a.wp = ws + R.r[D1A].img; a.in_t1 = x; a.epi = EPI_BIAS_ACT;
     DN_TIMED(s, "fwd3", 2.0 * N * H(0) * Wd(0) * p.c1k * 96 * 9, p.c1k, 96, H(0), Wd(0), N,
              launch_upconv3_x6(a, s));
   } else {
-    DN_TRY(deconv_forward(UP1, V(p.db[1], 2 * nf), V(p.c1, p.c1s, 0), s));
-    DN_TRY(conv_forward(D1A, V(p.c1, p.c1s), 1, V(p.d1a, 96), OUT_NHWC, s));
+    DN_TRY(deconv_forward(UP1, V(p.db[1], 2 * nf), V(p.c1, p.c1s, 0)));
+    DN_TRY(conv_forward(D1A, V(p.c1, p.c1s), V(p.d1a, 96)));
   }
-  // the head kernels' common arguments (their input: the activated dec_conv1b output, 96 -> 96)
-  auto head_in = [&](long off, int h) {
-    return fwd_args(V(off, 96), N, h, Wd(0), 96, 96, none, OUT_NHWC);
-  };
-  auto head_args = [&]() {
-    HeadArgs h{};
-    h.ba = Bs(NINA); h.bb = Bs(NINB);
-    h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-    h.y = y;
-    return h;
-  };
-  if (bf16) {  // dec_conv1b, nin_a, nin_b on the bf16 kernel, then nin_c (96 -> out_nc, fp32)
-    DN_TRY(conv_forward(D1B, V(p.d1a, 96), 1, V(p.d1b, 96), OUT_NHWC, s));
-    if (bf16_head_x6) {
-      FwdArgs a = head_in(p.d1b, H(0));
-      a.in_bf16 = bf16_store_out(D1B);  // d1b stored as bf16 by dec_conv1b
-      HeadArgs h = head_args();
-      h.wp = ws + p.packH;
-      DN_TIMED(s, "head", 2.0 * N * H(0) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0), Wd(0), N,
-               launch_nin_head_x6(a, h, ws + p.packH, s, /*bf16=*/true));
-      return DN_OK;
-    }
-    DN_TRY(conv_forward(NINA, V(p.d1b, 96), 1, V(p.na, 96), OUT_NHWC, s));
-    DN_TRY(conv_forward(NINB, V(p.na, 96), 1, V(p.nb, 96), OUT_NHWC, s));
-    const Layer& Lc = p.P.L[NINC];
-    DN_TRY(dn::conv_forward(V(p.nb, 96), N, H(0), Wd(0), Lc.cin, ws + p.packF[NINC], Bs(NINC),
-                            Lc.cout, Lc.k, 0, View{y, p.OC, 0}, OUT_NCHW, s));
-    return DN_OK;
-  }
-  // N2N no-grad pass (training_script.md:141-144 reads den at the pair pixels only): dec_conv1b
-  // and the head on those pixels, through the [N, H/2, W, 96] pair image in d1b's storage
-  if (sel) {
-    FwdArgs a = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
-    a.wp = ws + p.packX[D1B]; a.bias = Bs(D1B); a.epi = EPI_BIAS_ACT;
-    if (w6_sel) {  // the cells listed per tile orientation, then the Winograd pass over them
-      unsigned* list = reinterpret_cast<unsigned*>(ws + p.w6s_list);
-      int* cnt = reinterpret_cast<int*>(ws + p.w6s_cnt);
-      DN_TIMED(s, "fwd3sel", 2.0 * N * (H(0) / 2) * Wd(0) * 96 * 96 * 9, 96, 96, H(0) / 2, Wd(0), N,
-               launch_fwd_w6s(a, list, cnt, ws + p.packXV, s));
+
+  // dec_conv1b and the head (arch_unet.py:251-257).  The pair pass (training_script.md:141-144
+  // reads den at the pair pixels only) runs both on those pixels, through the [N, H/2, W, 96] pair
+  // image in d1b's storage
+  const int hh = R.sel ? H(0) / 2 : H(0);  // rows of the head's input
+  HeadArgs h{};
+  h.wp = ws + R.head_img;
+  h.ba = Bs(NINA); h.bb = Bs(NINB);
+  h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
+  h.y = y;
+  // the intermediate activations are written only when a backward will read them
+  if (p.with_bwd) { h.na = ws + p.na; h.nb = ws + p.nb; }
+  // the head kernels' input: the activated dec_conv1b output, 96 -> 96
+  FwdArgs a = fwd_args(V(p.d1b, 96), N, hh, Wd(0), 96, 96, none, OUT_NHWC);
+  const double head_flops = 2.0 * N * hh * Wd(0) * 96 * (2 * 96 + p.OC);
+  // dec_conv1b where it is not conv_forward's: the pair pass, the fp32 head kernel
+  FwdArgs ac = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
+  ac.wp = ws + R.r[D1B].img; ac.bias = Bs(D1B); ac.epi = EPI_BIAS_ACT;
+  if (R.sel) {
+    const OpTimer timer(s, "fwd3sel", 2.0 * N * hh * Wd(0) * 96 * 96 * 9, 96, 96, hh, Wd(0), N);
+    if (R.w6_sel) {  // the Winograd pass over the cells listed per tile orientation
+      DN_TRY(launch_fwd_w6s(ac, reinterpret_cast<unsigned*>(ws + p.w6s_list),
+                            reinterpret_cast<int*>(ws + p.w6s_cnt), ws + R.img_xv, s));
     } else {
-      a.sel_rd = sel_rd;
-      DN_TIMED(s, "fwd3sel", 2.0 * N * (H(0) / 2) * Wd(0) * 96 * 96 * 9, 96, 96, H(0) / 2, Wd(0), N,
-               launch_fwd_x6_sel(a, s));
+      ac.sel_rd = sel_rd;
+      DN_TRY(launch_fwd_x6_sel(ac, s));
     }
-    const FwdArgs ah = head_in(p.d1b, H(0) / 2);
-    HeadArgs h = head_args();
     h.rd = sel_rd;
-    DN_TIMED(s, "head", 2.0 * N * (H(0) / 2) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0) / 2,
-             Wd(0), N, launch_nin_head_x6(ah, h, ws + p.packH, s));
-    return DN_OK;
+  } else if (R.head != H_F32) {
+    DN_TRY(conv_forward(D1B, V(p.d1a, 96), V(p.d1b, 96)));
   }
-  if (x6) {  // dec_conv1b on the bf16x6 kernel, then the fused nin_a -> nin_b -> nin_c head
-    DN_TRY(conv_forward(D1B, V(p.d1a, 96), 1, V(p.d1b, 96), OUT_NHWC, s));
-    const FwdArgs a = head_in(p.d1b, H(0));
-    HeadArgs h = head_args();
-    h.wp = ws + p.packH;
-    if (p.with_bwd) { h.na = ws + p.na; h.nb = ws + p.nb; }
-    DN_TIMED(s, "head", 2.0 * N * H(0) * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, H(0), Wd(0), N,
-             head_x6 ? launch_nin_head_x6(a, h, ws + p.packH, s) : launch_nin_head(a, h, s));
-    return DN_OK;
-  }
-  // dec_conv1b + nin_a + nin_b + nin_c in one kernel (arch_unet.py:251-257); the
-  // intermediate activations are written only when a backward will read them
-  {
-    FwdArgs a = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
-    a.wp = ws + p.packF[D1B]; a.bias = Bs(D1B); a.epi = EPI_BIAS_ACT;
-    HeadArgs h = head_args();
-    h.wp = ws + p.packH;
-    if (p.with_bwd) { h.d1b = ws + p.d1b; h.na = ws + p.na; h.nb = ws + p.nb; }
-    DN_TIMED(s, "fwd3+head", 2.0 * N * H(0) * Wd(0) * 96 * (9 * 96 + 2 * 96 + p.OC), 96, 96, H(0),
-             Wd(0), N, launch_head(a, h, s));
+  switch (R.head) {
+    case H_F32:  // dec_conv1b inside the head kernel, on its fp32 image
+      if (p.with_bwd) h.d1b = ws + p.d1b;
+      DN_TIMED(s, "fwd3+head", 2.0 * N * H(0) * Wd(0) * 96 * (9 * 96 + 2 * 96 + p.OC), 96, 96, H(0),
+               Wd(0), N, launch_head(ac, h, s));
+      break;
+    case H_NIN:
+      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N, launch_nin_head(a, h, s));
+      break;
+    case H_NIN_X6:
+      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N,
+               launch_nin_head_x6(a, h, ws + R.head_img, s));
+      break;
+    case H_NIN_BF16:
+      a.in_bf16 = R.r[D1B].out_bf16;  // d1b stored as bf16 by dec_conv1b
+      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N,
+               launch_nin_head_x6(a, h, ws + R.head_img, s, /*bf16=*/true));
+      break;
+    case H_BF16_3: {
+      DN_TRY(conv_forward(NINA, V(p.d1b, 96), V(p.na, 96)));
+      DN_TRY(conv_forward(NINB, V(p.na, 96), V(p.nb, 96)));
+      const Layer& Lc = p.P.L[NINC];  // 96 -> out_nc, no activation, NCHW into y
+      DN_TRY(dn::conv_forward(V(p.nb, 96), N, H(0), Wd(0), Lc.cin, ws + R.r[NINC].img, Bs(NINC),
+                              Lc.cout, Lc.k, 0, View{y, p.OC, 0}, OUT_NCHW, s));
+      break;
+    }
   }
   return DN_OK;
+}
+
+}  // namespace
+
+dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y, float* ws,
+                       hipStream_t s, int prec, const uint8_t* sel_rd, int pack) {
+  const StreamDeviceGuard device_guard(s);
+  const FwdRoutes R = fwd_routes(p, prec, sel_rd != nullptr);
+  // (a prepacked forward: dn_unet_pack_weights left the images in ws)
+  if (pack != RUN_ONLY) {
+    const dn_status st = pack_forward(p, R, prm, ws, s);
+    if (st != DN_OK) return st;
+  }
+  return pack == PACK_ONLY ? DN_OK : run_forward(p, R, prm, x, y, ws, s, sel_rd);
 }
 
 // ------------------------------------------------------------------------------------
@@ -788,6 +847,44 @@ hipError_t side_fork(SideStream* side, hipStream_t s) {
 
 long tail_begin(const Plan& p) { return p.P.L[D5A].woff; }
 
+// The data-gradient route of every layer (enc_conv1 .. dec_conv1b), decided once: the pack loop
+// writes the image the launch reads
+namespace {
+enum BwdKind {
+  B_F32,     // conv data gradient on the fp32 kernel (Plan::packB)
+  B_X6,      // 3x3 on the bf16x6 kernels (packXB: zc-blocked image, tail as in the forward)
+  B_UP_F32,  // deconv data gradient on the fp32 kernel
+  B_UP_X6,   // ... of the 96-channel deconvs in the bf16x6 arithmetic (packUXB)
+};
+struct BwdRoute { int kind; long img; int zc; long wp_z; int tail; };
+struct BwdRoutes {
+  BwdRoute r[NL];
+  bool head_x6;  // the head's data gradients in the bf16x6 arithmetic (k_head_bwd_x6)
+};
+BwdRoutes bwd_routes(const Plan& p, int prec) {
+  const bool x6 = prec == DN_PREC_FP32_X6;
+  BwdRoutes B{};
+  for (int i = ENC1; i < NINA; ++i) {
+    const Layer& L = p.P.L[i];
+    BwdRoute& r = B.r[i];
+    if (L.deconv) {
+      r.kind = x6 && p.packUXB[i] >= 0 ? B_UP_X6 : B_UP_F32;
+      r.img = r.kind == B_UP_X6 ? p.packUXB[i] : p.packB[i];
+    } else if (x6 && p.packXB[i] >= 0) {
+      const int l = layer_level(i), nout = dgrad_nout(p, i);
+      r.kind = B_X6; r.img = p.packXB[i];
+      r.zc = x6_dgrad_zc(nout);
+      r.wp_z = x6_wp_z(L.cout, nout, r.zc);
+      r.tail = x6_image_mode(p.N, p.H >> l, p.W >> l, L.cout, nout, r.zc, true);
+    } else {
+      r.kind = B_F32; r.img = p.packB[i];
+    }
+  }
+  B.head_x6 = x6 && p.OC <= X6_HEAD_BWD_OCMAX;
+  return B;
+}
+}  // namespace
+
 dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float* dprm, float* dx,
                         float* ws, hipStream_t s, int prec, hipEvent_t tail_ready) {
   const StreamDeviceGuard device_guard(s);
@@ -799,28 +896,23 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   auto Wd = [&](int l) { return p.W >> l; };
   auto G = [&](int i) { return dprm + p.P.L[i].woff; };
   auto V = [&](long off, int stride, int coff = 0) { return View{ws + off, stride, coff}; };
-  auto x6_tail_b = [&](int i) -> int {  // as x6_tail_f in the forward, for the data gradients
-    const int l = layer_level(i), nout = dgrad_nout(p, i);
-    return x6_image_mode(N, H(l), Wd(l), p.P.L[i].cout, nout, x6_dgrad_zc(nout), true);
-  };
-  // bf16x6 data gradients of the 96-channel deconvs
-  auto x6_dgrad_deconv = [&](int i) { return x6 && p.packUXB[i] >= 0; };
+  const BwdRoutes B = bwd_routes(p, prec);
   // deconv layer i: dy at the layer's output level -> dx one level below (* leaky'(mask))
   auto deconv_dgrad = [&](int i, const View& dy, const View& mask, int epi, const View& dx,
                           hipStream_t st) -> hipError_t {
     const Layer& L = p.P.L[i];
+    const BwdRoute& r = B.r[i];
     const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
     const OpTimer timer(st, "deconv_dgrad", 2.0 * N * h * w * L.cin * L.cout * 4, L.cout, L.cin, h,
                         w, N);
-    if (!x6_dgrad_deconv(i))
-      return dn::deconv_dgrad(dy, N, h, w, L.cout, ws + p.packB[i], L.cin, mask, epi, dx, st);
+    if (r.kind == B_UP_F32)
+      return dn::deconv_dgrad(dy, N, h, w, L.cout, ws + r.img, L.cin, mask, epi, dx, st);
     FwdArgs a = fwd_args(dy, 2 * h, 2 * w, N, h, w, L.cout, L.cin, dx, OUT_NHWC);
     a.epi = epi;
     set_mask(a, mask);
-    return launch_deconv_dgrad_x6(a, ws + p.packUXB[i], st);
+    return launch_deconv_dgrad_x6(a, ws + r.img, st);
   };
-  // the head's data gradients in the bf16x6 arithmetic (k_head_bwd_x6)
-  const bool head_bwd_x6 = x6 && p.OC <= X6_HEAD_BWD_OCMAX;
+  const bool head_bwd_x6 = B.head_x6;
   // g_nb (the nin_b output's gradient) recomputed by nin_b's weight gradient (k_wgrad1p<., GNB>)
   // from nb and dy instead of being stored by k_head_bwd_x6 and read back (384 B per pixel less)
   const bool head_gnb = head_bwd_x6;
@@ -831,20 +923,24 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     auto add = [&](bool ok, const PackJob& j) { return ok ? pack_add(pb, j, s) : hipErrorInvalidValue; };
     for (int i = ENC1; i < NINA; ++i) {
       const Layer& L = p.P.L[i];
+      const BwdRoute& r = B.r[i];
       const float* w = prm + L.woff;
       PackJob j;
-      if (L.deconv && x6_dgrad_deconv(i)) {
-        DN_TRY(add(true, pack_job_deconv_dgrad_x6(w, ws + p.packUXB[i])));
-      } else if (L.deconv) {
-        DN_TRY(add(pack_job(G_DN2, deconv_dgrad_view(w, L.cout), L.cout, L.cin, 1, ws + p.packB[i],
-                            0, 0, j), j));
-      } else if (x6 && p.packXB[i] >= 0) {
-        const int nout = dgrad_nout(p, i);
-        DN_TRY(add(pack_job_x6(conv_dgrad_view(w, L.cin, 3), L.cout, nout, x6_dgrad_zc(nout),
-                               ws + p.packXB[i], x6_tail_b(i), j), j));
-      } else {
-        DN_TRY(add(pack_job(L.k == 3 ? G_C3 : G_C1, conv_dgrad_view(w, L.cin, L.k), L.cout,
-                            dgrad_nout(p, i), 1, ws + p.packB[i], 0, 0, j), j));
+      switch (r.kind) {
+        case B_UP_X6:
+          DN_TRY(add(true, pack_job_deconv_dgrad_x6(w, ws + r.img)));
+          break;
+        case B_UP_F32:
+          DN_TRY(add(pack_job(G_DN2, deconv_dgrad_view(w, L.cout), L.cout, L.cin, 1, ws + r.img, 0, 0, j), j));
+          break;
+        case B_X6:
+          DN_TRY(add(pack_job_x6(conv_dgrad_view(w, L.cin, 3), L.cout, dgrad_nout(p, i), r.zc,
+                                 ws + r.img, r.tail, j), j));
+          break;
+        case B_F32:
+          DN_TRY(add(pack_job(L.k == 3 ? G_C3 : G_C1, conv_dgrad_view(w, L.cin, L.k), L.cout,
+                              dgrad_nout(p, i), 1, ws + r.img, 0, 0, j), j));
+          break;
       }
     }
     if (head_bwd_x6)
@@ -876,18 +972,18 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   auto conv_dgrad = [&](int i, const View& dz, int epi, const View& mask, const View& dx,
                         hipStream_t st) -> hipError_t {
     const Layer& L = p.P.L[i];
+    const BwdRoute& r = B.r[i];
     const int l = layer_level(i), h = H(l), w = Wd(l), cout = L.cout, nout = dgrad_nout(p, i);
     const OpTimer timer(st, L.k == 3 ? "dgrad3" : "dgrad1",
                         2.0 * N * h * w * cout * nout * L.k * L.k, cout, nout, h, w, N);
-    if (!x6 || p.packXB[i] < 0)  // (packXB: the 3x3 layers)
-      return dn::conv_dgrad(dz, N, h, w, cout, ws + p.packB[i], nout, L.k, epi, mask, dx, st);
+    if (r.kind == B_F32)
+      return dn::conv_dgrad(dz, N, h, w, cout, ws + r.img, nout, L.k, epi, mask, dx, st);
     FwdArgs a = fwd_args(dz, N, h, w, cout, nout, dx, OUT_NHWC);
-    a.zc = x6_dgrad_zc(nout);
-    a.wp = ws + p.packXB[i];
-    a.wp_z = a.zc ? x6_pack_elems(cout, nout, a.zc) / ((nout + a.zc - 1) / a.zc) : 0;
+    a.zc = r.zc;
+    a.wp = ws + r.img; a.wp_z = r.wp_z;
     a.epi = epi;
     set_mask(a, mask);
-    a.x6_tail = x6_tail_b(i);
+    a.x6_tail = r.tail;
     return launch_fwd_x6(a, st);
   };
   const View none{nullptr, 0, 0};
@@ -929,10 +1025,10 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   DN_TRY(fork());
   // (head_gnb: the gradient operand g_nb recomputed from nb and dy inside k_wgrad1p, which also
   // forms nin_c's weight gradient from those reads into nin_c's slab)
+  const WgradHead hd{head_gnb ? OC : 0, dyv.p, dyv.stride, prm + p.P.L[NINC].woff,
+                     fold_c ? SL(NINC) + 64 : nullptr, G(NINC)};
   DN_TRY(wgrad(W_C1, head_gnb ? V(p.nb, 96) : V(p.g_nb, 96), V(p.na, 96), N, H(0), Wd(0), 96, 96,
-               G(NINB), SL(NINB), p.splits[NINB], s2, x6, Z, &rb,
-               head_gnb ? OC : 0, dyv.p, dyv.stride, prm + p.P.L[NINC].woff,
-               fold_c ? SL(NINC) + 64 : nullptr, G(NINC)));
+               G(NINB), SL(NINB), p.splits[NINB], s2, x6, Z, &rb, &hd));
   DN_TRY(fork());
   DN_TRY(wgrad(W_C1, V(p.g_na, 96), V(p.d1b, 96), N, H(0), Wd(0), 96, 96, G(NINA), SL(NINA),
                p.splits[NINA], s2, x6, Z, &rb));

@@ -132,12 +132,17 @@ hipError_t deconv_forward(const View& x, int N, int h, int w, int cin, const flo
                           const float* b, int cout, const View& out, hipStream_t s);
 hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const float* wp, int cin,
                         const View& mask, int epi, const View& dx, hipStream_t s);
+// nin_b's weight gradient only (WgradArgs::head_gnb, hd_*): the gradient operand recomputed from
+// nb and dy, nin_c's weight gradient formed from the same reads
+struct WgradHead {
+  int gnb; const float* dy; int dy_stride; const float* wc;
+  float* slab_c; float* dwc;
+};
 // slab: [64 floats | splits x (W + b)]; zeros == nullptr: the 64 floats are zeroed here and
 // serve as the DMA padding; rb: the reduction is queued, not launched
 hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
                  float* dwb, float* slab, int splits, hipStream_t s, bool x6 = false,
-                 const float* zeros = nullptr, RedBatch* rb = nullptr, int head_gnb = 0,
-                 const float* hd_dy = nullptr, int hd_dy_stride = 0, const float* hd_wc = nullptr,
-                 float* hd_slab_c = nullptr, float* hd_dwc = nullptr);
+                 const float* zeros = nullptr, RedBatch* rb = nullptr,
+                 const WgradHead* head = nullptr);
 
 }  // namespace dn
