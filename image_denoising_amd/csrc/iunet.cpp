@@ -17,10 +17,6 @@
 //     f = leaky(fuse(cc_k)), then ResBlock(RDB(f))      UpBlock, arch_unet.py:454-472
 //   y = sigmoid(final([x_up3 | x]))                      arch_unet.py:530-531
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "iunet.h"
 #include "iunet_ops.h"
@@ -39,12 +35,6 @@ namespace {
     }                                                                     \
   } while (0)
 
-// a launch of a pass body, skipped in its dry run (Ctx::dry)
-#define IU_RUN(c, x)                 \
-  do {                               \
-    if (!(c).dry) IU_TRY(x);         \
-  } while (0)
-
 constexpr int GROWTH = 32;  // RDB growth (arch_unet.py:437)
 constexpr float GN_EPS = 1e-5f;
 
@@ -54,13 +44,20 @@ int gn_groups(int ch) {  // norm2d('gn', ch, groups=32), arch_unet.py:12-15
   return g;
 }
 
-// ---- generic convolution on the MFMA kernel --------------------------------------------
-struct GGeom {
-  int gather = G_C3, nt = 6, np = 96, nz = 1;
-  long img = 0;  // floats of one z-block's packed image
+// ---- routes: the kernel and the weight image of one conv launch -------------------------
+// A pass resolves them once per conv site (iunet_fwd_routes / iunet_bwd_routes below); the pack
+// loop writes exactly the image a route names and the launch reads it, neither decides anything.
+struct IRoute {
+  bool x6 = false;             // the bf16x6 kernels (else the fp32 MFMA kernel)
+  int tail = 0, zc = 0;        // x6: image mode (x6_image_mode / x6_tail_mode), output-channel
+  long wp_z = 0;               //   blocks over blockIdx.z and the bf16 elements of one
+  int gather = G_C3, nt = 6, np = 96, nz = 1;  // fp32: tile width (np = 16 nt), z-blocks
+  long img = 0;                //   floats of one z-block's packed image
+  long floats = 0;             // the whole image (0: the site launches nothing in this pass)
+  long off = 0;                // its offset in the arena
 };
 
-bool ggeom(int ksize, int K, int nout, GGeom& g) {
+bool ggeom(int ksize, int K, int nout, IRoute& g) {
   g.gather = ksize == 3 ? G_C3 : G_C1;
   const int nts[3] = {6, 3, 2};
   // relative cost per output channel of the tile widths; with few reduction channels (K < 64:
@@ -105,76 +102,68 @@ bool x6_takes(int K, int nout, int tail) {
 // output-channel blocks of the wide layers: 96, or 48 where 96 would pad (144 = 3 x 48)
 int x6_zc(int nout) { return nout <= 96 ? 0 : (nout % 96 == 0 ? 96 : 48); }
 
-long gpack_floats(int ksize, int K, int nout) {
-  GGeom g;
-  if (!ggeom(ksize, K, nout, g)) return -1;
-  return g.img * g.nz;
+// The route of a k x k conv with K reduction channels and nout outputs over N x h x w pixels.
+// The views count through their alignment only: x6 images tail-pack a partial last K chunk when
+// the launch takes the pipelined kernel (aligned input), and x6_image_mode may add X6_W6 where
+// the output / auxiliary views allow the Winograd kernel's float4 NHWC epilogue.
+// false: no kernel has a weight image for this shape.
+bool resolve_route(int prec, int ksize, int N, int h, int w, int K, int nout, const IView& in,
+                   const IView& out, int layout, const IView& aux, IRoute& r) {
+  r = IRoute{};
+  if (prec == DN_PREC_FP32_X6 && ksize == 3) {
+    const int zc = x6_zc(nout);
+    const bool aligned = ((in.stride | in.off | K) & 3) == 0;
+    const bool w6_ok = layout == OUT_NHWC && ((out.stride | out.off | nout) & 3) == 0 &&
+                       (aux.o < 0 || ((aux.stride | aux.off) & 3) == 0);
+    const int tail = w6_ok && aligned ? x6_image_mode(N, h, w, K, nout, zc, true)
+                     : aligned && x6_pipelined(N, h, w, nout, zc) ? x6_tail_mode(K) : 0;
+    if (x6_takes(K, nout, tail)) {
+      const long elems = x6_pack_elems(K, nout, zc);  // bf16
+      if (elems <= 0) return false;
+      r.x6 = true; r.tail = tail; r.zc = zc;
+      r.wp_z = x6_wp_z(K, nout, zc);
+      r.floats = (elems + 1) / 2;
+      return true;
+    }
+  }
+  if (!ggeom(ksize, K, nout, r)) return false;
+  r.floats = r.img * r.nz;
+  return true;
 }
 
-// forward image of conv weight [cout][cin][k][k] (reduction K = cin, outputs = cout)
-bool gjob_fwd(const float* w, int ksize, int cin, int cout, float* out, PackJob& j) {
-  GGeom g;
-  if (!ggeom(ksize, cin, cout, g)) return false;
-  WView wv = conv_fwd_view(w, cin, ksize);
-  wv.sZ = (long)g.np * wv.sN;
-  return pack_job(g.gather, wv, cin, g.np, g.nz, out, g.np, cout, j);
+// floats of a site's arena slot: the larger of the two precisions' images (for a 3x3 the bf16x6
+// image of every shape x6_takes may route; -1 where those kernels have no tile)
+long slot_floats(int ksize, int K, int nout) {
+  IRoute g;
+  long f = ggeom(ksize, K, nout, g) ? g.img * g.nz : -1;
+  if (ksize == 3) f = std::max(f, (x6_pack_elems(K, nout, x6_zc(nout)) + 1) / 2);
+  return (std::max(f, 0L) + 63) / 64 * 64;
 }
 
-// data-gradient image: reduction over the layer's cout, outputs = its first nout input channels
-bool gjob_dgrad(const float* w, int ksize, int cin_total, int cout, int nout, float* out,
-                PackJob& j) {
-  GGeom g;
-  if (!ggeom(ksize, cout, nout, g)) return false;
-  WView wv = conv_dgrad_view(w, cin_total, ksize);
-  wv.sZ = (long)g.np * wv.sN;
-  return pack_job(g.gather, wv, cout, g.np, g.nz, out, g.np, nout, j);
-}
-
-hipError_t grun(int ksize, const View& in, int N, int H, int W, int K, const float* wp, int nout,
-                const float* bias, int epi, const View& out, int layout, const View& aux,
-                hipStream_t s) {
-  GGeom g;
-  if (!ggeom(ksize, K, nout, g)) return hipErrorInvalidValue;
-  FwdArgs a = fwd_args(in, N, H, W, K, nout, out, layout);
-  a.wp = wp; a.wp_z = g.img;
+// the launch of a resolved conv on its packed image wp
+hipError_t run_conv(const IRoute& r, const float* wp, const View& in, int N, int h, int w, int K,
+                    int nout, const float* bias, int epi, const View& out, int layout,
+                    const View& aux, hipStream_t s) {
+  FwdArgs a = fwd_args(in, N, h, w, K, nout, out, layout);
+  a.wp = wp;
   a.bias = bias; a.epi = epi;
   set_mask(a, aux);
-  a.zc = g.np;
-  return launch_fwd_nt(g.gather, g.nt, a, s);
-}
-
-// the same 3x3 conv on the split-bf16 kernels (image from launch_pack_x6 with zc = x6_zc(nout))
-// tail packing of a partial last K chunk when the launch takes the pipelined kernel
-// (w6_ok: the launch's output / auxiliary views allow the Winograd kernel's float4 NHWC
-// epilogue; then x6_image_mode may add X6_W6 for the 96-channel blocks)
-int x6_tail_for(const View& in, int N, int H, int W, int K, int nout, bool w6_ok) {
-  const bool aligned = ((in.stride | in.off | K) & 3) == 0;
-  if (w6_ok && aligned) return x6_image_mode(N, H, W, K, nout, x6_zc(nout), true);
-  return aligned && x6_pipelined(N, H, W, nout, x6_zc(nout)) ? x6_tail_mode(K) : 0;
-}
-static bool w6_views(const View& out, int layout, const View& aux, int nout) {
-  return layout == OUT_NHWC && ((out.stride | out.off | nout) & 3) == 0 &&
-         (!aux.p || ((aux.stride | aux.off) & 3) == 0);
-}
-
-hipError_t x6run(const View& in, int N, int H, int W, int K, const float* wp, int nout,
-                 const float* bias, int epi, const View& out, int layout, const View& aux,
-                 int tail, hipStream_t s) {
-  FwdArgs a = fwd_args(in, N, H, W, K, nout, out, layout);
-  a.x6_tail = tail;
-  a.zc = x6_zc(nout);
-  a.wp = wp; a.wp_z = x6_wp_z(K, nout, a.zc);
-  a.bias = bias; a.epi = epi;
-  set_mask(a, aux);
-  return launch_fwd_x6(a, s);
+  if (r.x6) {
+    a.x6_tail = r.tail;
+    a.zc = r.zc; a.wp_z = r.wp_z;
+    return launch_fwd_x6(a, s);
+  }
+  a.zc = r.np; a.wp_z = r.img;
+  return launch_fwd_nt(r.gather, r.nt, a, s);
 }
 
 // ---- parameter layout (state_dict order of ImprovedUNet) ---------------------------------
 struct Alloc {
   long off = 0;
+  int convs = 0;
   IConv conv(int cout, int cin, int k, bool bias = true) {
     IConv c;
-    c.cout = cout; c.cin = cin; c.k = k;
+    c.cout = cout; c.cin = cin; c.k = k; c.idx = convs++;
     c.w = off; off += (long)cout * cin * k * k;
     if (bias) { c.b = off; off += cout; }
     return c;
@@ -203,36 +192,6 @@ struct Alloc {
     return r;
   }
 };
-
-// every conv the backward runs a weight gradient for: (mode, level resolution shift, cin, cout)
-struct WJob { int mode, lvl, cin, cout; };
-
-void wgrad_jobs(const IParams& P, std::vector<WJob>& v) {
-  auto rdb = [&](const IRdb& r, int l) {
-    for (int j = 0; j < 4; ++j) v.push_back({W_C3, l, r.conv[j].cin, GROWTH});
-    v.push_back({W_C1, l, r.lff.cin, r.C});
-  };
-  auto res = [&](const IRes& r, int l) {
-    v.push_back({W_C3, l, r.C, r.C});
-    v.push_back({W_C3, l, r.C, r.C});
-  };
-  v.push_back({W_C3, 0, 48, 1});  // ne2
-  for (int i = 0; i < 4; ++i) {
-    if (i > 0) v.push_back({W_C3, i, P.down[i].conv.cin, P.down[i].conv.cout});
-    rdb(P.down[i].rdb, i);
-    res(P.down[i].res, i);
-  }
-  rdb(P.brdb, 4);
-  res(P.bres, 4);
-  for (int k = 0; k < 4; ++k) {
-    const IUp& u = P.up[k];
-    v.push_back({W_C3, 4 - k, u.ps.cin, u.ps.cout});
-    v.push_back({W_C3, 3 - k, u.fuse.cin, u.fuse.cout});
-    rdb(u.rdb, 3 - k);
-    res(u.res, 3 - k);
-  }
-  v.push_back({W_C3, 0, P.fin.cin, P.fin.cout});
-}
 
 }  // namespace
 
@@ -328,6 +287,10 @@ bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err) {
   }
   P.fin = A.conv(P.OC, 24 + P.C, 3);  // final (:515)
   P.total = A.off;
+  if (A.convs != kIConvs) {
+    err = "ImprovedUNet: the parameter layout does not have kIConvs convolutions";
+    return false;
+  }
   return true;
 }
 
@@ -382,43 +345,6 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
   p.sc = allocf((long)N * 384);
   p.sh = allocf((long)N * 384);
   p.gpart = allocf(2L * 2 * std::max(2048L, (long)N) * 384);  // N*S splits x 384 ch x 2 doubles
-  // packed-weight arena: one slot per conv of a pass (forward images; the backward's
-  // data-gradient images reuse the region), each sized for the fp32 or the split-bf16 image,
-  // whichever the launch takes.  A pass packs every slot in a few batched launches first.
-  long fsum = 0, bsum = 0;
-  auto slot = [](int k, int K, int nout) {
-    long f = gpack_floats(k, K, nout);
-    if (k == 3)  // every shape x6_takes may route (-1 where the x6 kernels have no tile)
-      f = std::max(f, (x6_pack_elems(K, nout, x6_zc(nout)) + 1) / 2);
-    return (std::max(f, 0L) + 63) / 64 * 64;
-  };
-  auto pf = [&](int k, int K, int nout) { fsum += slot(k, K, nout); };
-  auto pb = [&](int k, int K, int nout) { bsum += slot(k, K, nout); };
-  for (int i = 0; i < 4; ++i) {
-    const ILevel& L = P.down[i];
-    pf(3, L.conv.cin, L.conv.cout);
-    if (i > 0) pb(3, L.conv.cout, L.conv.cin);
-  }
-  auto rdbp = [&](const IRdb& r) {
-    for (int j = 0; j < 4; ++j) { pf(3, r.conv[j].cin, GROWTH); pb(3, GROWTH, r.conv[j].cin); }
-    pf(1, r.lff.cin, r.C); pb(1, r.C, r.lff.cin);
-  };
-  auto resp = [&](const IRes& r) {
-    for (int t = 0; t < 2; ++t) { pf(3, r.C, r.C); pb(3, r.C, r.C); }
-  };
-  for (int i = 0; i < 4; ++i) { rdbp(P.down[i].rdb); resp(P.down[i].res); }
-  rdbp(P.brdb); resp(P.bres);
-  for (int k = 0; k < 4; ++k) {
-    const IUp& u = P.up[k];
-    pf(3, u.ps.cin, u.ps.cout); pb(3, u.ps.cout, u.ps.cin);
-    pf(3, u.fuse.cin, u.fuse.cout); pb(3, u.fuse.cout, u.fuse.cin);
-    rdbp(u.rdb); resp(u.res);
-  }
-  pb(3, 1, 48);         // ne2 data gradient
-  pb(3, P.OC, 24);      // final data gradient (x_up3 part)
-  const long arena = bwd ? std::max(fsum, bsum) : fsum;
-  p.pack = allocf(arena);
-  p.pack_floats = arena;
   if (bwd) {
     auto gblock = [&](IBlockBufs& b, int l, int ch) {
       b.dF = alloc(l, ch + 4 * GROWTH);
@@ -449,12 +375,100 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
     p.ca = allocf((long)N * 384);
     p.cb = allocf((long)N * 384);
     p.ccf = allocf((long)N * 384);
-    // weight-gradient slab: 64 zero floats + max over layers of splits x (W + b)
-    std::vector<WJob> jobs;
-    wgrad_jobs(P, jobs);
-    long slab = 0;
-    for (const WJob& j : jobs)
-      slab = std::max(slab, gwgrad_slab_floats(j.mode, N, H >> j.lvl, W >> j.lvl, j.cin, j.cout));
+  }
+  // ---- the conv sites: every convolution's place in the dataflow, stated once (after every
+  // buffer they name is allocated; the arena and the slab, sized from them, follow) ----
+  for (ISite& s : p.site) s = ISite{};
+  auto V = [](long o, int stride, int ch = 0) { return IView{o, stride, ch}; };
+  const IView none;
+  auto input = [&](const IConv& L, int l, IView in) {
+    ISite& s = p.site[L.idx];
+    s.L = L; s.lvl = l; s.in = in;
+  };
+  auto fwd = [&](const IConv& L, int l, IView in, int epi, IView out, int layout = OUT_NHWC,
+                 IView aux = IView{}) {
+    input(L, l, in);
+    ISite& s = p.site[L.idx];
+    s.epi = epi; s.out = out; s.layout = layout; s.aux = aux;
+  };
+  // gradients from g = dL/d(conv output): the blocked weight gradient, and the data gradient of
+  // the first nout input channels into dx (plans with a backward only: the views are its buffers)
+  auto grad = [&](const IConv& L, IView g, int nout, int depi, IView daux, IView dx) {
+    if (!bwd) return;
+    ISite& s = p.site[L.idx];
+    s.wmode = L.k == 3 ? W_C3 : W_C1;
+    s.g = g; s.nout = nout; s.depi = depi; s.daux = daux; s.dx = dx;
+  };
+  // F[:, :C] holds the block input; the growth convs read prefixes of F and write their slice,
+  // lff adds the input back (out = x + lff(F)) into b.r
+  auto rdb = [&](const IRdb& R, const IBlockBufs& b, int l) {
+    const int C = R.C, FS = C + 4 * GROWTH;
+    const IView F = V(b.F, FS), dF = V(b.dF, FS);
+    for (int j = 0; j < 4; ++j) {
+      const int o = C + GROWTH * j;
+      fwd(R.conv[j], l, F, EPI_BIAS_ACT, V(b.F, FS, o));
+      grad(R.conv[j], V(b.dzj[j], GROWTH), o, EPI_ACCUM, none, dF);
+    }
+    fwd(R.lff, l, F, EPI_BIAS_ADD, V(b.r, C), OUT_NHWC, F);
+    grad(R.lff, V(b.dr, C), FS, EPI_PLAIN, none, dF);
+  };
+  // r -> conv1 -> z1 -GN1, leaky-> a1 -> conv2 -> z2 -GN2-> (+ r); dout = the gradient of the
+  // block's output: d r = conv1^T(dz1) + dout (the residual; EPI_BIAS_ADD with no bias)
+  auto res = [&](const IRes& R, const IBlockBufs& b, int l, IView dout) {
+    const int C = R.C;
+    fwd(R.c1, l, V(b.r, C), EPI_PLAIN, V(b.z1, C));
+    grad(R.c1, V(b.dz1, C), C, EPI_BIAS_ADD, dout, V(b.dr, C));
+    fwd(R.c2, l, V(b.a1, C), EPI_PLAIN, V(b.z2, C));
+    grad(R.c2, V(b.dz2, C), C, EPI_MASK, V(b.a1, C), V(b.dg1, C));
+  };
+  // ne0, ne2 and the final conv run their forward on the thin kernels (launched by the pass), ne0
+  // and the level-0 conv (C + 1 < 16 input channels) their whole backward
+  input(P.ne0, 0, none);
+  input(P.ne2, 0, V(p.h, 48));
+  grad(P.ne2, V(p.dsg, 4), 48, EPI_MASK, V(p.h, 48), V(p.dh, 48));
+  for (int i = 0; i < 4; ++i) {
+    const IConv& L = P.down[i].conv;
+    const int out = P.up[3 - i].out;  // s_i lives in the skip slice of up block 3-i's concat
+    fwd(L, i, i == 0 ? V(p.x0, 4) : V(p.pool[i], L.cin), EPI_BIAS_ACT,
+        V(p.dl[i].F, L.cout + 4 * GROWTH));
+    if (i > 0) grad(L, V(p.dza[i], L.cout), L.cin, EPI_PLAIN, none, V(p.dpool, L.cin));
+    rdb(P.down[i].rdb, p.dl[i], i);
+    res(P.down[i].res, p.dl[i], i, V(p.dcc[3 - i], 3 * out, out));
+  }
+  rdb(P.brdb, p.bb, 4);
+  res(P.bres, p.bb, 4, V(p.dxb, 384));
+  for (int k = 0; k < 4; ++k) {
+    const IUp& u = P.up[k];
+    const int l = 3 - k, out = u.out;
+    // conv_ps reads the bottle output or the previous up block's, one level below its block
+    fwd(u.ps, l + 1, k == 0 ? V(p.xb, 384) : V(p.xu[k - 1], u.in), EPI_BIAS, V(p.cc[k], 3 * out),
+        OUT_PS);
+    grad(u.ps, V(p.dps[k], 4 * out), u.in, EPI_PLAIN, none,
+         k == 0 ? V(p.dxb, 384) : V(p.dxu[k - 1], u.in));
+    fwd(u.fuse, l, V(p.cc[k], 3 * out), EPI_BIAS_ACT, V(p.ul[k].F, out + 4 * GROWTH));
+    grad(u.fuse, V(p.ul[k].dzf, out), 3 * out, EPI_PLAIN, none, V(p.dcc[k], 3 * out));
+    rdb(u.rdb, p.ul[k], l);
+    // the last block's output gradient: the final conv's data gradient, in dh[:, :24] (dh's 48
+    // channels are free until the noise estimator's backward)
+    res(u.res, p.ul[k], l, k < 3 ? V(p.dxu[k], out) : V(p.dh, 24));
+  }
+  input(P.fin, 0, V(p.cf, 28));
+  grad(P.fin, V(p.dzfin, 4), 24, EPI_PLAIN, none, V(p.dh, 24));  // x_up3's 24 of the concat
+  // packed-weight arena: the forward's images, one slot per site that launches on the generic
+  // kernels (the backward's data-gradient images reuse the region).  A pass packs the images its
+  // routes name in a few batched launches first.
+  long fsum = 0, bsum = 0, slab = 0;
+  for (const ISite& s : p.site) {
+    if (s.out.o >= 0) fsum += slot_floats(s.L.k, s.L.cin, s.L.cout);
+    if (s.nout) bsum += slot_floats(s.L.k, s.L.cout, s.nout);
+    if (s.wmode >= 0)
+      slab = std::max(slab, gwgrad_slab_floats(s.wmode, N, H >> s.lvl, W >> s.lvl, s.L.cin, s.L.cout));
+  }
+  p.pack_floats = std::max(fsum, bsum);
+  p.pack = allocf(p.pack_floats);
+  if (bwd) {
+    // weight-gradient slab: 64 zero floats + max over sites of splits x (W + b); the level-0
+    // conv's thin kernel
     const int st = enc0_wgrad_splits(N, H, W);
     slab = std::max(slab, (long)st * (48L * (P.C + 1) * 9 + 48));
     p.slab = off;
@@ -466,179 +480,175 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
 }
 
 // ------------------------------------------------------------------------------------
-// forward
+// routes, packing and the launches of one conv site
 // ------------------------------------------------------------------------------------
 namespace {
 
-// Optional per-op timing (DN_PROFILE_OPS=1): HIP events around every conv / weight gradient /
-// GroupNorm call, aggregated by shape and printed to stderr at the end of each pass.  One record
-// list per host thread (thread_local g_prof below: no state shared between callers); a failing
-// HIP event call switches this thread's profiling off with a message, it never fails a pass.
-struct OpProf {
-  struct Rec { std::string label; double flops; hipEvent_t a, b; };
-  bool on = getenv("DN_PROFILE_OPS") != nullptr;
-  std::vector<Rec> recs;
-  bool ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    fprintf(stderr, "[dn ops] %s failed (%s): per-op timing off\n", what, hipGetErrorString(e));
-    on = false;
-    return false;
-  }
-  void drop() {
-    for (auto& r : recs) {
-      if (r.a) (void)hipEventDestroy(r.a);
-      if (r.b) (void)hipEventDestroy(r.b);
-    }
-    recs.clear();
-  }
-  void flush(const char* pass) {
-    if (!on || recs.empty()) return;
-    if (!ok(hipEventSynchronize(recs.back().b), "hipEventSynchronize")) return drop();
-    struct Agg { double ms = 0, flops = 0; int n = 0; };
-    std::vector<std::pair<std::string, Agg>> agg;
-    double total = 0;
-    for (auto& r : recs) {
-      float ms = 0;
-      if (!ok(hipEventElapsedTime(&ms, r.a, r.b), "hipEventElapsedTime")) return drop();
-      total += ms;
-      auto it = std::find_if(agg.begin(), agg.end(), [&](auto& x) { return x.first == r.label; });
-      if (it == agg.end()) { agg.push_back({r.label, Agg{}}); it = agg.end() - 1; }
-      it->second.ms += ms; it->second.flops += r.flops; it->second.n += 1;
-    }
-    const size_t nrec = recs.size();
-    drop();
-    std::sort(agg.begin(), agg.end(), [](auto& x, auto& y) { return x.second.ms > y.second.ms; });
-    fprintf(stderr, "[dn ops] %s: %.3f ms in %zu ops\n", pass, total, nrec);
-    for (auto& [l, a] : agg)
-      fprintf(stderr, "  %8.3f ms  %7.1f TF/s  x%-3d %s\n", a.ms,
-              a.flops > 0 ? a.flops / (a.ms * 1e-3) / 1e12 : 0.0, a.n, l.c_str());
-  }
-};
-thread_local OpProf g_prof;
+struct IRoutes { IRoute r[kIConvs]; };
 
-// dn_profile_ops op name of an OpScope kind ("fwd" + k = 3 -> "fwd3", the bench's 3x3 ops)
-inline const char* prof_op(const char* kind, int k) {
-  const std::string kd(kind);
-  if (kd == "fwd") return k == 3 ? "fwd3" : "fwd1";
-  if (kd == "wgrad") return k == 3 ? "wgrad3" : "wgrad1";
-  if (kd == "dgrad") return k == 3 ? "dgrad3" : "dgrad1";
-  return kind;
-}
-
-struct OpScope {
-  hipStream_t s;
-  bool on;
-  OpTimer timer;  // the in-step launch record (dn_profile_ops), when enabled
-  OpScope(hipStream_t st, const char* kind, int cout, int cin, int k, int h, int w, int N,
-          double flop_mult)
-      : s(st), on(g_prof.on),
-        timer(st, prof_op(kind, k), flop_mult * 2.0 * N * h * w * (double)cout * cin * k * k,
-              cin, cout, h, w, N) {
-    if (!on) return;
-    char b[128];
-    snprintf(b, sizeof(b), "%-6s %dx%d k%d @%dx%d", kind, cout, cin, k, h, w);
-    OpProf::Rec r{b, flop_mult * 2.0 * N * h * w * (double)cout * cin * k * k, nullptr, nullptr};
-    if (!g_prof.ok(hipEventCreate(&r.a), "hipEventCreate") ||
-        !g_prof.ok(hipEventCreate(&r.b), "hipEventCreate") ||
-        !g_prof.ok(hipEventRecord(r.a, s), "hipEventRecord")) {
-      if (r.a) (void)hipEventDestroy(r.a);
-      if (r.b) (void)hipEventDestroy(r.b);
-      on = false;
-      g_prof.drop();
-      return;
-    }
-    g_prof.recs.push_back(r);
-  }
-  ~OpScope() {
-    if (on && g_prof.on && !g_prof.recs.empty() &&
-        !g_prof.ok(hipEventRecord(g_prof.recs.back().b, s), "hipEventRecord"))
-      g_prof.drop();
-  }
-};
+const View kNone{nullptr, 0, 0};
 
 struct Ctx {
   const IPlan& p;
+  const IRoutes& R;
   const float* prm;
   float* ws;
   hipStream_t s;
   int prec;
-  // backward: the weight gradients' stream (s when running on one stream) and its fork event
-  hipStream_t s2 = nullptr;
-  hipEvent_t fork = nullptr;
-  // A pass runs twice: dry (every conv queues its weight image into the next arena slot, nothing
-  // else launches), then the batched packs, then for real (each conv takes the same slot).
-  bool dry = false;
-  PackBatch* pb = nullptr;
-  long* next = nullptr;
+  SideStream* side;  // backward: the weight gradients' stream and fork event (nullptr: all on s)
   View V(long o, int stride, int off = 0) const { return View{ws + o, stride, off}; }
-  float* slot(long floats) const {  // the next conv's arena slot (nullptr: arena overrun)
-    const long o = *next;
-    *next += (floats + 63) / 64 * 64;
-    return *next <= p.pack_floats ? ws + p.pack + o : nullptr;
-  }
+  View V(const IView& v) const { return v.o < 0 ? kNone : View{ws + v.o, v.stride, v.off}; }
+  const ISite& site(const IConv& c) const { return p.site[c.idx]; }
+  const float* image(const IConv& c) const { return ws + p.pack + R.r[c.idx].off; }
   const float* Wt(const IConv& c) const { return prm + c.w; }
   const float* Bs(const IConv& c) const { return c.b >= 0 ? prm + c.b : nullptr; }
 };
 
-const View kNone{nullptr, 0, 0};
+// places r's image behind the pass's earlier ones in the arena
+void place(IRoute& r, long& next) {
+  r.off = next;
+  next += (r.floats + 63) / 64 * 64;
+}
 
-dn_status conv_fwd(const Ctx& c, const IConv& L, const View& in, int h, int w, int epi,
-                   const View& out, int layout = OUT_NHWC, const View& aux = kNone) {
-  const int tail = x6_tail_for(in, c.p.N, h, w, L.cin, L.cout, w6_views(out, layout, aux, L.cout));
-  const bool x6 = c.prec == DN_PREC_FP32_X6 && L.k == 3 && x6_takes(L.cin, L.cout, tail);
-  float* pk = c.slot(x6 ? (x6_pack_elems(L.cin, L.cout, x6_zc(L.cout)) + 1) / 2
-                        : gpack_floats(L.k, L.cin, L.cout));
-  if (!pk) {
-    set_error("ImprovedUNet: packed-weight arena overrun (forward)");
-    return DN_ERR_ARG;
-  }
-  if (c.dry) {
-    PackJob j;
-    const bool ok = x6 ? pack_job_x6(conv_fwd_view(c.Wt(L), L.cin, 3), L.cin, L.cout,
-                                     x6_zc(L.cout), pk, tail, j)
-                       : gjob_fwd(c.Wt(L), L.k, L.cin, L.cout, pk, j);
-    if (!ok) {
+// The forward route of every site that launches on the generic kernels, in the order the pass
+// runs them (= state_dict order).  The arena holds them: every slot is at least its route's image.
+dn_status iunet_fwd_routes(const IPlan& p, int prec, IRoutes& R) {
+  long next = 0;
+  for (int i = 0; i < kIConvs; ++i) {
+    const ISite& s = p.site[i];
+    if (s.out.o < 0) continue;
+    if (!resolve_route(prec, s.L.k, p.N, p.H >> s.lvl, p.W >> s.lvl, s.L.cin, s.L.cout, s.in,
+                       s.out, s.layout, s.aux, R.r[i])) {
       set_error("ImprovedUNet: no weight image for a forward conv");
       return DN_ERR_ARG;
     }
-    IU_TRY(pack_add(*c.pb, j, c.s));
-    return DN_OK;
+    place(R.r[i], next);
   }
-  OpScope prof(c.s, "fwd", L.cout, L.cin, L.k, h, w, c.p.N, 1.0);
-  if (x6)
-    IU_TRY(x6run(in, c.p.N, h, w, L.cin, pk, L.cout, c.Bs(L), epi, out, layout, aux, tail, c.s));
-  else
-    IU_TRY(grun(L.k, in, c.p.N, h, w, L.cin, pk, L.cout, c.Bs(L), epi, out, layout, aux, c.s));
   return DN_OK;
+}
+
+// ... and the data-gradient routes (reduction over the conv's outputs, the first nout input
+// channels out), the backward's order: the forward's reversed
+dn_status iunet_bwd_routes(const IPlan& p, int prec, IRoutes& R) {
+  long next = 0;
+  for (int i = kIConvs - 1; i >= 0; --i) {
+    const ISite& s = p.site[i];
+    if (!s.nout) continue;
+    if (!resolve_route(prec, s.L.k, p.N, p.H >> s.lvl, p.W >> s.lvl, s.L.cout, s.nout, s.g, s.dx,
+                       OUT_NHWC, s.daux, R.r[i])) {
+      set_error("ImprovedUNet: no weight image for a data gradient");
+      return DN_ERR_ARG;
+    }
+    place(R.r[i], next);
+  }
+  return DN_OK;
+}
+
+// packs the images the pass's routes name, in the pass's order (24 images per launch)
+dn_status pack_images(const Ctx& c, bool bwd) {
+  PackBatch pb;
+  for (int n = 0; n < kIConvs; ++n) {
+    const int i = bwd ? kIConvs - 1 - n : n;
+    const IRoute& r = c.R.r[i];
+    if (!r.floats) continue;
+    const IConv& L = c.p.site[i].L;
+    // forward image of the weight [cout][cin][k][k]: reduction K = cin, outputs = cout; data
+    // gradient: reduction over cout, outputs = the first nout input channels
+    const int K = bwd ? L.cout : L.cin, nout = bwd ? c.p.site[i].nout : L.cout;
+    WView wv = bwd ? conv_dgrad_view(c.Wt(L), L.cin, L.k) : conv_fwd_view(c.Wt(L), L.cin, L.k);
+    float* out = c.ws + c.p.pack + r.off;
+    PackJob j;
+    if (!r.x6) wv.sZ = (long)r.np * wv.sN;
+    if (!(r.x6 ? pack_job_x6(wv, K, nout, r.zc, out, r.tail, j)
+               : pack_job(r.gather, wv, K, r.np, r.nz, out, r.np, nout, j))) {
+      set_error("ImprovedUNet: no weight image for a conv");
+      return DN_ERR_ARG;
+    }
+    IU_TRY(pack_add(pb, j, c.s));
+  }
+  IU_TRY(pack_flush(pb, c.s));
+  return DN_OK;
+}
+
+double conv_flops(int N, int h, int w, int cout, int cin, int k) {
+  return 2.0 * N * h * w * (double)cout * cin * k * k;
+}
+
+dn_status conv_fwd(const Ctx& c, const IConv& L) {
+  const ISite& s = c.site(L);
+  const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
+  const OpTimer timer(c.s, L.k == 3 ? "fwd3" : "fwd1", conv_flops(N, h, w, L.cout, L.cin, L.k),
+                      L.cin, L.cout, h, w, N);
+  IU_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.in), N, h, w, L.cin, L.cout, c.Bs(L), s.epi,
+                  c.V(s.out), s.layout, c.V(s.aux), c.s));
+  return DN_OK;
+}
+
+// dx (the site's first nout input channels) = conv^T(g) with its epilogue (daux = mask / residual)
+dn_status dgrad_g(const Ctx& c, const IConv& L) {
+  const ISite& s = c.site(L);
+  const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
+  const OpTimer timer(c.s, L.k == 3 ? "dgrad3" : "dgrad1", conv_flops(N, h, w, s.nout, L.cout, L.k),
+                      L.cout, s.nout, h, w, N);
+  IU_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.g), N, h, w, L.cout, s.nout, nullptr, s.depi,
+                  c.V(s.dx), OUT_NHWC, c.V(s.daux), c.s));
+  return DN_OK;
+}
+
+// dW (+ db) of a conv from g = dL/d(conv output) and its forward input; written into dprm
+dn_status wgrad_g(const Ctx& c, float* dprm, const IConv& L) {
+  const ISite& s = c.site(L);
+  const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
+  // on the side stream, behind the main stream's work so far (g is its latest output)
+  const hipStream_t s2 = c.side ? c.side->st : c.s;
+  IU_TRY(side_fork(c.side, c.s));
+  const OpTimer timer(s2, L.k == 3 ? "wgrad3" : "wgrad1", conv_flops(N, h, w, L.cout, L.cin, L.k),
+                      L.cin, L.cout, h, w, N);
+  const int taps = s.wmode == W_C3 ? 9 : 1;
+  const bool bias = L.b >= 0;
+  if (bias && L.b != L.w + (long)L.cout * L.cin * taps) {
+    set_error("ImprovedUNet: bias does not follow its weight");
+    return DN_ERR_ARG;
+  }
+  return gwgrad_run(s.wmode, c.V(s.g), c.V(s.in), N, h, w, L.cin, L.cout, bias, c.prec,
+                    dprm + L.w, c.ws + c.p.slab, s2);
 }
 
 dn_status gn_fwd(const Ctx& c, const IGN& g, const View& z, int h, int w, float* stats, int act,
                  const View* res, const View& out) {
-  if (c.dry) return DN_OK;
-  OpScope prof(c.s, "gn", g.C, 1, 1, h, w, c.p.N, 0.0);
+  const OpTimer timer(c.s, "gn", 0.0, 1, g.C, h, w, c.p.N);
   return gn_forward(z, c.p.N, (long)h * w, g.C, g.G, c.prm + g.g, c.prm + g.b, act, res, out, stats,
                     reinterpret_cast<double*>(c.ws + c.p.gpart), c.ws + c.p.sc, c.ws + c.p.sh,
                     c.s);
 }
 
-// F[:, :C] holds the block input; writes the RDB output to b.r
-dn_status rdb_fwd(const Ctx& c, const IRdb& R, const IBlockBufs& b, int h, int w) {
-  const int C = R.C, FS = C + 4 * GROWTH;
-  for (int j = 0; j < 4; ++j)
-    if (dn_status st = conv_fwd(c, R.conv[j], c.V(b.F, FS), h, w, EPI_BIAS_ACT,
-                                c.V(b.F, FS, C + GROWTH * j)))
-      return st;
-  return conv_fwd(c, R.lff, c.V(b.F, FS), h, w, EPI_BIAS_ADD, c.V(b.r, C), OUT_NHWC, c.V(b.F, FS));
+dn_status gn_bwd(const Ctx& c, float* dprm, const IGN& g, const View& dy, const View& z, int h,
+                 int w, const float* stats, const View& dz) {
+  const OpTimer timer(c.s, "gnbwd", 0.0, 1, g.C, h, w, c.p.N);
+  return gn_backward(dy, z, c.p.N, (long)h * w, g.C, g.G, c.prm + g.g, stats, dz, dprm + g.g,
+                     dprm + g.b, reinterpret_cast<double*>(c.ws + c.p.gpart), c.ws + c.p.ca,
+                     c.ws + c.p.cb, c.ws + c.p.ccf, c.s);
 }
 
+// ------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------
+// F[:, :C] holds the block input; writes the RDB output to b.r
+dn_status rdb_fwd(const Ctx& c, const IRdb& R) {
+  for (int j = 0; j < 4; ++j)
+    if (dn_status st = conv_fwd(c, R.conv[j])) return st;
+  return conv_fwd(c, R.lff);
+}
+
+// GN1 takes conv1's output to conv2's input, GN2 conv2's output (+ the block input) to `out`
 dn_status res_fwd(const Ctx& c, const IRes& R, const IBlockBufs& b, int h, int w, const View& out) {
-  const int C = R.C;
-  const View r = c.V(b.r, C);
-  if (dn_status st = conv_fwd(c, R.c1, r, h, w, EPI_PLAIN, c.V(b.z1, C))) return st;
-  if (dn_status st = gn_fwd(c, R.n1, c.V(b.z1, C), h, w, c.ws + b.st1, 1, nullptr, c.V(b.a1, C)))
+  const ISite &s1 = c.site(R.c1), &s2 = c.site(R.c2);
+  const View r = c.V(s1.in);
+  if (dn_status st = conv_fwd(c, R.c1)) return st;
+  if (dn_status st = gn_fwd(c, R.n1, c.V(s1.out), h, w, c.ws + b.st1, 1, nullptr, c.V(s2.in)))
     return st;
-  if (dn_status st = conv_fwd(c, R.c2, c.V(b.a1, C), h, w, EPI_PLAIN, c.V(b.z2, C))) return st;
-  return gn_fwd(c, R.n2, c.V(b.z2, C), h, w, c.ws + b.st2, 0, &r, out);
+  if (dn_status st = conv_fwd(c, R.c2)) return st;
+  return gn_fwd(c, R.n2, c.V(s2.out), h, w, c.ws + b.st2, 0, &r, out);
 }
 
 WView thin_view(const float* w, int cin) {  // weight [o][cin][3][3] as W(o, k, t)
@@ -647,7 +657,6 @@ WView thin_view(const float* w, int cin) {  // weight [o][cin][3][3] as W(o, k, 
   return v;
 }
 
-// the forward's launches (Ctx::dry: only the convs' weight images are queued)
 dn_status forward_body(const Ctx& c, const float* x, float* y) {
   const IPlan& p = c.p;
   const float* prm = c.prm;
@@ -656,76 +665,62 @@ dn_status forward_body(const Ctx& c, const float* x, float* y) {
   const IParams& P = p.P;
   const int N = p.N, H = p.H, W = p.W, C = P.C;
   // noise estimator: h = leaky(ne0(x)) (also writes x into x0[:, :C], zeros x0[:, C:4])
-  IU_RUN(c, launch_enc0_fwd(x, N, C, H, W, prm + P.ne0.w, prm + P.ne0.b, ws + p.h, ws + p.x0, 4,
-                            0, 4, nullptr, s));
-  IU_RUN(c, launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48),
-                              prm + P.ne2.b, TE_SIGMOID, kNone, c.V(p.x0, 4, C), 0, 1, s));
+  IU_TRY(launch_enc0_fwd(x, N, C, H, W, prm + P.ne0.w, prm + P.ne0.b, ws + p.h, ws + p.x0, 4, 0, 4,
+                         nullptr, s));
+  IU_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48), prm + P.ne2.b,
+                           TE_SIGMOID, kNone, c.V(p.x0, 4, C), 0, 1, s));
   if (p.with_bwd) {
-    IU_RUN(c, hipMemcpyAsync(ws + p.xin, x, sizeof(float) * (size_t)N * C * H * W,
-                             hipMemcpyDeviceToDevice, s));
-    IU_RUN(c, launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48),
-                                prm + P.ne2.b, TE_SIGMOID, kNone, View{ws + p.sig, 0, 0}, 1, 1, s));
+    IU_TRY(hipMemcpyAsync(ws + p.xin, x, sizeof(float) * (size_t)N * C * H * W,
+                          hipMemcpyDeviceToDevice, s));
+    IU_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48),
+                             prm + P.ne2.b, TE_SIGMOID, kNone, View{ws + p.sig, 0, 0}, 1, 1, s));
   }
-  IU_RUN(c, launch_nchw_to_slice(x, N, C, H, W, ws + p.cf, 28, 24, 28, s));  // final concat input
+  IU_TRY(launch_nchw_to_slice(x, N, C, H, W, ws + p.cf, 28, 24, 28, s));  // final concat input
   // encoder
-  View xi = c.V(p.x0, 4);
   for (int i = 0; i < 4; ++i) {
     const ILevel& L = P.down[i];
-    const int h = H >> i, w = W >> i, nf = L.conv.cout, FS = nf + 4 * GROWTH;
-    const IBlockBufs& b = p.dl[i];
-    if (dn_status st = conv_fwd(c, L.conv, xi, h, w, EPI_BIAS_ACT, c.V(b.F, FS))) return st;
-    if (dn_status st = rdb_fwd(c, L.rdb, b, h, w)) return st;
+    const int h = H >> i, w = W >> i, nf = L.conv.cout;
+    if (dn_status st = conv_fwd(c, L.conv)) return st;
+    if (dn_status st = rdb_fwd(c, L.rdb)) return st;
     const int k = 3 - i, out = P.up[k].out;  // skip slice of up block k's concat
     const View skip = c.V(p.cc[k], 3 * out, out);
-    if (dn_status st = res_fwd(c, L.res, b, h, w, skip)) return st;
+    if (dn_status st = res_fwd(c, L.res, p.dl[i], h, w, skip)) return st;
     const View dst = i < 3 ? c.V(p.pool[i + 1], nf) : c.V(p.bb.F, 384 + 4 * GROWTH);
-    IU_RUN(c, launch_vpool_fwd(skip, N, h, w, nf, dst, s));
-    xi = dst;
+    IU_TRY(launch_vpool_fwd(skip, N, h, w, nf, dst, s));
   }
   // bottleneck
-  if (dn_status st = rdb_fwd(c, P.brdb, p.bb, H >> 4, W >> 4)) return st;
+  if (dn_status st = rdb_fwd(c, P.brdb)) return st;
   if (dn_status st = res_fwd(c, P.bres, p.bb, H >> 4, W >> 4, c.V(p.xb, 384))) return st;
   // decoder
-  View xk = c.V(p.xb, 384);
   for (int k = 0; k < 4; ++k) {
     const IUp& u = P.up[k];
-    const int l = 3 - k, h = H >> l, w = W >> l, out = u.out, FS = out + 4 * GROWTH;
-    const IBlockBufs& b = p.ul[k];
-    if (dn_status st = conv_fwd(c, u.ps, xk, h / 2, w / 2, EPI_BIAS, c.V(p.cc[k], 3 * out), OUT_PS))
-      return st;
-    if (dn_status st = conv_fwd(c, u.fuse, c.V(p.cc[k], 3 * out), h, w, EPI_BIAS_ACT, c.V(b.F, FS)))
-      return st;
-    if (dn_status st = rdb_fwd(c, u.rdb, b, h, w)) return st;
-    const View o = k < 3 ? c.V(p.xu[k], out) : c.V(p.cf, 28);
-    if (dn_status st = res_fwd(c, u.res, b, h, w, o)) return st;
-    xk = o;
+    const int l = 3 - k, h = H >> l, w = W >> l;
+    if (dn_status st = conv_fwd(c, u.ps)) return st;
+    if (dn_status st = conv_fwd(c, u.fuse)) return st;
+    if (dn_status st = rdb_fwd(c, u.rdb)) return st;
+    const View o = k < 3 ? c.V(p.xu[k], u.out) : c.V(p.cf, 28);
+    if (dn_status st = res_fwd(c, u.res, p.ul[k], h, w, o)) return st;
   }
-  IU_RUN(c, launch_conv3_thin(c.V(p.cf, 28), N, H, W, 24 + C, thin_view(prm + P.fin.w, 24 + C),
-                              prm + P.fin.b, TE_SIGMOID, kNone, View{y, 0, 0}, 1, P.OC, s));
+  IU_TRY(launch_conv3_thin(c.V(p.cf, 28), N, H, W, 24 + C, thin_view(prm + P.fin.w, 24 + C),
+                           prm + P.fin.b, TE_SIGMOID, kNone, View{y, 0, 0}, 1, P.OC, s));
   if (p.with_bwd)
-    IU_RUN(c, hipMemcpyAsync(ws + p.yout, y, sizeof(float) * (size_t)N * P.OC * H * W,
-                             hipMemcpyDeviceToDevice, s));
+    IU_TRY(hipMemcpyAsync(ws + p.yout, y, sizeof(float) * (size_t)N * P.OC * H * W,
+                          hipMemcpyDeviceToDevice, s));
   return DN_OK;
 }
 
 }  // namespace
 
-// Every pass: a dry run queues the weight image of each conv into its arena slot, the queued
-// packs launch (24 images per launch), then the pass runs on them.
+// Every pass: resolve the routes, pack the images they name, run on them.
 dn_status iunet_forward(const IPlan& p, const float* prm, const float* x, float* y, float* ws,
                         hipStream_t s, int prec) {
   const StreamDeviceGuard device_guard(s);
   if (prec != DN_PREC_FP32 && prec != DN_PREC_FP32_X6) return DN_ERR_ARG;
-  PackBatch pb;
-  long next = 0;
-  Ctx c{p, prm, ws, s, prec};
-  c.pb = &pb; c.next = &next; c.dry = true;
-  if (dn_status st = forward_body(c, x, y)) return st;
-  IU_TRY(pack_flush(pb, s));
-  next = 0; c.dry = false;
-  if (dn_status st = forward_body(c, x, y)) return st;
-  g_prof.flush("iunet forward");
-  return DN_OK;
+  IRoutes R;
+  if (dn_status st = iunet_fwd_routes(p, prec, R)) return st;
+  const Ctx c{p, R, prm, ws, s, prec, nullptr};
+  if (dn_status st = pack_images(c, false)) return st;
+  return forward_body(c, x, y);
 }
 
 // ------------------------------------------------------------------------------------
@@ -733,152 +728,69 @@ dn_status iunet_forward(const IPlan& p, const float* prm, const float* x, float*
 // ------------------------------------------------------------------------------------
 namespace {
 
-// dW (+ db) of a conv from g = dL/d(conv output) and its input x; written into dprm
-dn_status wgrad_g(const Ctx& c, float* dprm, int mode, const IConv& L, const View& g, const View& x,
-                  int h, int w) {
-  if (c.dry) return DN_OK;
-  // on the side stream, behind the main stream's work so far (g is its latest output)
-  const hipStream_t s2 = c.s2 ? c.s2 : c.s;
-  if (s2 != c.s) {
-    IU_TRY(hipEventRecord(c.fork, c.s));
-    IU_TRY(hipStreamWaitEvent(s2, c.fork, 0));
-  }
-  OpScope prof(s2, "wgrad", L.cout, L.cin, L.k, h, w, c.p.N, 1.0);
-  const int taps = mode == W_C3 ? 9 : 1;
-  const bool bias = L.b >= 0;
-  if (bias && L.b != L.w + (long)L.cout * L.cin * taps) {
-    set_error("ImprovedUNet: bias does not follow its weight");
-    return DN_ERR_ARG;
-  }
-  return gwgrad_run(mode, g, x, c.p.N, h, w, L.cin, L.cout, bias, c.prec, dprm + L.w,
-                    c.ws + c.p.slab, s2);
-}
-
-// dx (first nout input channels) = conv^T(g) with epilogue epi (aux = mask / residual)
-dn_status dgrad_g(const Ctx& c, const IConv& L, const View& g, int h, int w, int nout, int epi,
-                  const View& aux, const View& dx) {
-  const int tail = x6_tail_for(g, c.p.N, h, w, L.cout, nout, w6_views(dx, OUT_NHWC, aux, nout));
-  const bool x6 = c.prec == DN_PREC_FP32_X6 && L.k == 3 && x6_takes(L.cout, nout, tail);
-  float* pk = c.slot(x6 ? (x6_pack_elems(L.cout, nout, x6_zc(nout)) + 1) / 2
-                        : gpack_floats(L.k, L.cout, nout));
-  if (!pk) {
-    set_error("ImprovedUNet: packed-weight arena overrun (backward)");
-    return DN_ERR_ARG;
-  }
-  if (c.dry) {
-    PackJob j;
-    const bool ok = x6 ? pack_job_x6(conv_dgrad_view(c.Wt(L), L.cin, 3), L.cout, nout,
-                                     x6_zc(nout), pk, tail, j)
-                       : gjob_dgrad(c.Wt(L), L.k, L.cin, L.cout, nout, pk, j);
-    if (!ok) {
-      set_error("ImprovedUNet: no weight image for a data gradient");
-      return DN_ERR_ARG;
-    }
-    IU_TRY(pack_add(*c.pb, j, c.s));
-    return DN_OK;
-  }
-  OpScope prof(c.s, "dgrad", nout, L.cout, L.k, h, w, c.p.N, 1.0);
-  if (x6)
-    IU_TRY(x6run(g, c.p.N, h, w, L.cout, pk, nout, nullptr, epi, dx, OUT_NHWC, aux, tail, c.s));
-  else
-    IU_TRY(grun(L.k, g, c.p.N, h, w, L.cout, pk, nout, nullptr, epi, dx, OUT_NHWC, aux, c.s));
-  return DN_OK;
-}
-
-dn_status gn_bwd(const Ctx& c, float* dprm, const IGN& g, const View& dy, const View& z, int h,
-                 int w, const float* stats, const View& dz) {
-  if (c.dry) return DN_OK;
-  OpScope prof(c.s, "gnbwd", g.C, 1, 1, h, w, c.p.N, 0.0);
-  return gn_backward(dy, z, c.p.N, (long)h * w, g.C, g.G, c.prm + g.g, stats, dz, dprm + g.g,
-                     dprm + g.b, reinterpret_cast<double*>(c.ws + c.p.gpart), c.ws + c.p.ca,
-                     c.ws + c.p.cb, c.ws + c.p.ccf, c.s);
-}
-
-// ResBlock backward: dout -> b.dr (gradient of the block input r)
-dn_status res_bwd(const Ctx& c, float* dprm, const IRes& R, const IBlockBufs& b, const View& dout,
-                  int h, int w) {
-  const int C = R.C;
-  if (dn_status st = gn_bwd(c, dprm, R.n2, dout, c.V(b.z2, C), h, w, c.ws + b.st2, c.V(b.dz2, C)))
+// ResBlock backward: the block's output gradient (c1's residual view) -> b.dr (gradient of the
+// block input r)
+dn_status res_bwd(const Ctx& c, float* dprm, const IRes& R, const IBlockBufs& b, int h, int w) {
+  const ISite &s1 = c.site(R.c1), &s2 = c.site(R.c2);
+  if (dn_status st = gn_bwd(c, dprm, R.n2, c.V(s1.daux), c.V(s2.out), h, w, c.ws + b.st2, c.V(s2.g)))
     return st;
-  if (dn_status st = wgrad_g(c, dprm, W_C3, R.c2, c.V(b.dz2, C), c.V(b.a1, C), h, w)) return st;
-  if (dn_status st = dgrad_g(c, R.c2, c.V(b.dz2, C), h, w, C, EPI_MASK, c.V(b.a1, C), c.V(b.dg1, C)))
+  if (dn_status st = wgrad_g(c, dprm, R.c2)) return st;
+  if (dn_status st = dgrad_g(c, R.c2)) return st;
+  if (dn_status st = gn_bwd(c, dprm, R.n1, c.V(s2.dx), c.V(s1.out), h, w, c.ws + b.st1, c.V(s1.g)))
     return st;
-  if (dn_status st = gn_bwd(c, dprm, R.n1, c.V(b.dg1, C), c.V(b.z1, C), h, w, c.ws + b.st1,
-                            c.V(b.dz1, C)))
-    return st;
-  if (dn_status st = wgrad_g(c, dprm, W_C3, R.c1, c.V(b.dz1, C), c.V(b.r, C), h, w)) return st;
-  // d r = conv1^T(dz1) + dout  (the residual), EPI_BIAS_ADD with no bias
-  return dgrad_g(c, R.c1, c.V(b.dz1, C), h, w, C, EPI_BIAS_ADD, dout, c.V(b.dr, C));
+  if (dn_status st = wgrad_g(c, dprm, R.c1)) return st;
+  return dgrad_g(c, R.c1);
 }
 
 // RDB backward: b.dr (gradient of the RDB output) -> b.dF[:, :C] (gradient of the block input)
 dn_status rdb_bwd(const Ctx& c, float* dprm, const IRdb& R, const IBlockBufs& b, int h, int w) {
   const int C = R.C, FS = C + 4 * GROWTH;
   const long npx = (long)c.p.N * h * w;
-  const View dr = c.V(b.dr, C);
-  if (dn_status st = wgrad_g(c, dprm, W_C1, R.lff, dr, c.V(b.F, FS), h, w)) return st;
-  if (dn_status st = dgrad_g(c, R.lff, dr, h, w, FS, EPI_PLAIN, kNone, c.V(b.dF, FS))) return st;
-  IU_RUN(c, launch_vadd(c.V(b.dF, FS), dr, npx, C, c.s));  // out = x + lff(...)
+  if (dn_status st = wgrad_g(c, dprm, R.lff)) return st;
+  if (dn_status st = dgrad_g(c, R.lff)) return st;
+  IU_TRY(launch_vadd(c.V(b.dF, FS), c.V(b.dr, C), npx, C, c.s));  // out = x + lff(...)
   for (int j = 3; j >= 0; --j) {
     const int o = C + GROWTH * j;
-    const View dzj = c.V(b.dzj[j], GROWTH);
-    IU_RUN(c, launch_vmask(dzj, c.V(b.dF, FS, o), c.V(b.F, FS, o), npx, GROWTH, c.s));
-    if (dn_status st = wgrad_g(c, dprm, W_C3, R.conv[j], dzj, c.V(b.F, FS), h, w)) return st;
-    if (dn_status st = dgrad_g(c, R.conv[j], dzj, h, w, o, EPI_ACCUM, kNone,
-                               c.V(b.dF, FS)))
-      return st;
+    IU_TRY(launch_vmask(c.V(b.dzj[j], GROWTH), c.V(b.dF, FS, o), c.V(b.F, FS, o), npx, GROWTH, c.s));
+    if (dn_status st = wgrad_g(c, dprm, R.conv[j])) return st;
+    if (dn_status st = dgrad_g(c, R.conv[j])) return st;
   }
   return DN_OK;
 }
 
-// the backward's launches (Ctx::dry: only the data gradients' weight images are queued)
-dn_status backward_body(const Ctx& c, const float* dy, float* dprm, SideStream* side) {
+dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
   const IPlan& p = c.p;
   const float* prm = c.prm;
   float* ws = c.ws;
   const hipStream_t s = c.s;
-  const hipStream_t s2 = side ? side->st : s;
-  auto fork = [&] { return side_fork(side, s); };
+  const hipStream_t s2 = c.side ? c.side->st : s;
   const IParams& P = p.P;
   const int N = p.N, H = p.H, W = p.W, C = P.C, OC = P.OC;
   const long HW = (long)H * W;
   // final: dz = dy * y(1-y)  (stride-4 NHWC), then its weight / data gradients
-  IU_RUN(c, launch_dsigmoid_nchw(ws + p.yout, dy, N, OC, HW, ws + p.dzfin, 4, s));
-  if (dn_status st = wgrad_g(c, dprm, W_C3, P.fin, c.V(p.dzfin, 4), c.V(p.cf, 28), H, W)) return st;
-  // gradient of x_up3 = the first 24 channels of the final concat (the input slice needs
-  // none); dh (48 channels) is free until the noise estimator's backward
-  IU_RUN(c, hipMemsetAsync(ws + p.dsg, 0, sizeof(float) * 4 * (size_t)N * HW, s));
-  const View dfin = c.V(p.dh, 24);
-  if (dn_status st = dgrad_g(c, P.fin, c.V(p.dzfin, 4), H, W, 24, EPI_PLAIN, kNone, dfin)) return st;
+  IU_TRY(launch_dsigmoid_nchw(ws + p.yout, dy, N, OC, HW, ws + p.dzfin, 4, s));
+  if (dn_status st = wgrad_g(c, dprm, P.fin)) return st;
+  // gradient of x_up3 = the first 24 channels of the final concat (the input slice needs none)
+  IU_TRY(hipMemsetAsync(ws + p.dsg, 0, sizeof(float) * 4 * (size_t)N * HW, s));
+  if (dn_status st = dgrad_g(c, P.fin)) return st;
   // decoder, last block first
-  View dcur = dfin;
   for (int k = 3; k >= 0; --k) {
     const IUp& u = P.up[k];
     const int l = 3 - k, h = H >> l, w = W >> l, out = u.out, FS = out + 4 * GROWTH;
     const IBlockBufs& b = p.ul[k];
-    if (dn_status st = res_bwd(c, dprm, u.res, b, dcur, h, w)) return st;
+    if (dn_status st = res_bwd(c, dprm, u.res, b, h, w)) return st;
     if (dn_status st = rdb_bwd(c, dprm, u.rdb, b, h, w)) return st;
     // f = leaky(fuse(cc)): dz = dF[:, :out] * leaky'(f)
-    const View dzf = c.V(b.dzf, out);
-    IU_RUN(c, launch_vmask(dzf, c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, out, s));
-    if (dn_status st = wgrad_g(c, dprm, W_C3, u.fuse, dzf, c.V(p.cc[k], 3 * out), h, w)) return st;
-    if (dn_status st = dgrad_g(c, u.fuse, dzf, h, w, 3 * out, EPI_PLAIN, kNone,
-                               c.V(p.dcc[k], 3 * out)))
-      return st;
+    IU_TRY(launch_vmask(c.V(b.dzf, out), c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, out, s));
+    if (dn_status st = wgrad_g(c, dprm, u.fuse)) return st;
+    if (dn_status st = dgrad_g(c, u.fuse)) return st;
     // PixelShuffle backward, then conv_ps (input: bottle output or the previous up block)
-    float* gps = ws + p.dps[k];
-    IU_RUN(c, launch_unshuffle(c.V(p.dcc[k], 3 * out), N, h / 2, w / 2, out, gps, s));
-    const View xin = k == 0 ? c.V(p.xb, 384) : c.V(p.xu[k - 1], u.in);
-    if (dn_status st = wgrad_g(c, dprm, W_C3, u.ps, View{gps, 4 * out, 0}, xin, h / 2, w / 2))
-      return st;
-    const View dxin = k == 0 ? c.V(p.dxb, 384) : c.V(p.dxu[k - 1], u.in);
-    if (dn_status st = dgrad_g(c, u.ps, View{gps, 4 * out, 0}, h / 2, w / 2, u.in, EPI_PLAIN,
-                               kNone, dxin))
-      return st;
-    dcur = dxin;
+    IU_TRY(launch_unshuffle(c.V(p.dcc[k], 3 * out), N, h / 2, w / 2, out, ws + p.dps[k], s));
+    if (dn_status st = wgrad_g(c, dprm, u.ps)) return st;
+    if (dn_status st = dgrad_g(c, u.ps)) return st;
   }
   // bottleneck: its input is pool(s_3), living in bb.F[:, :384]
-  if (dn_status st = res_bwd(c, dprm, P.bres, p.bb, c.V(p.dxb, 384), H >> 4, W >> 4)) return st;
+  if (dn_status st = res_bwd(c, dprm, P.bres, p.bb, H >> 4, W >> 4)) return st;
   if (dn_status st = rdb_bwd(c, dprm, P.brdb, p.bb, H >> 4, W >> 4)) return st;
   View dpooled = c.V(p.bb.dF, 384 + 4 * GROWTH);  // d x_4 (first 384 channels)
   // encoder, deepest level first
@@ -889,17 +801,14 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm, SideStream* 
     const int k = 3 - i, out = P.up[k].out;
     const View skip = c.V(p.cc[k], 3 * out, out), dskip = c.V(p.dcc[k], 3 * out, out);
     // d s_i = (skip gradient from the fuse conv) + maxpool backward of d x_{i+1}
-    IU_RUN(c, launch_vpool_bwd_acc(skip, N, h, w, nf, dpooled, dskip, s));
-    if (dn_status st = res_bwd(c, dprm, L.res, b, dskip, h, w)) return st;
+    IU_TRY(launch_vpool_bwd_acc(skip, N, h, w, nf, dpooled, dskip, s));
+    if (dn_status st = res_bwd(c, dprm, L.res, b, h, w)) return st;
     if (dn_status st = rdb_bwd(c, dprm, L.rdb, b, h, w)) return st;
     const View dza = c.V(p.dza[i], nf);
-    IU_RUN(c, launch_vmask(dza, c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, nf, s));
+    IU_TRY(launch_vmask(dza, c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, nf, s));
     if (i > 0) {
-      const View xi = c.V(p.pool[i], L.conv.cin);
-      if (dn_status st = wgrad_g(c, dprm, W_C3, L.conv, dza, xi, h, w)) return st;
-      if (dn_status st = dgrad_g(c, L.conv, dza, h, w, L.conv.cin, EPI_PLAIN, kNone,
-                                 c.V(p.dpool, L.conv.cin)))
-        return st;
+      if (dn_status st = wgrad_g(c, dprm, L.conv)) return st;
+      if (dn_status st = dgrad_g(c, L.conv)) return st;
       dpooled = c.V(p.dpool, L.conv.cin);
     } else {
       // level-0 conv: input x0 = [x | sigma] with C+1 < 16 channels -> the thin wgrad kernel on
@@ -907,37 +816,34 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm, SideStream* 
       float* slab = ws + p.slab;
       const long n = 48L * (C + 1) * 9 + 48;
       const int st = enc0_wgrad_splits(N, H, W);
-      IU_RUN(c, fork());
-      IU_RUN(c, launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.xin, N, C, H, W, slab, n, C + 1, 0,
-                                     1, st, s2));
-      IU_RUN(c, launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.sig, N, 1, H, W, slab, n, C + 1, C,
-                                     0, st, s2));
-      IU_RUN(c, launch_reduce(slab, n, st, n, dprm + L.conv.w, s2));
+      IU_TRY(side_fork(c.side, s));
+      IU_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.xin, N, C, H, W, slab, n, C + 1, 0, 1,
+                                  st, s2));
+      IU_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.sig, N, 1, H, W, slab, n, C + 1, C, 0,
+                                  st, s2));
+      IU_TRY(launch_reduce(slab, n, st, n, dprm + L.conv.w, s2));
       // d sigma (channel C of x0) through the sigmoid: flipped weight column ci = C
       WView fv{};
       fv.w = prm + L.conv.w; fv.off = (long)C * 9; fv.sN = 9; fv.sK = (long)(C + 1) * 9;
       fv.sT = 1; fv.taps = 9; fv.flip = 1;
-      IU_RUN(c, launch_conv3_thin(dza, N, H, W, 48, fv, nullptr, TE_DSIG, c.V(p.x0, 4, C),
-                                  c.V(p.dsg, 4), 0, 1, s));
+      IU_TRY(launch_conv3_thin(dza, N, H, W, 48, fv, nullptr, TE_DSIG, c.V(p.x0, 4, C),
+                               c.V(p.dsg, 4), 0, 1, s));
     }
   }
   // noise estimator: ne2 (48 -> 1) and ne0 (C -> 48)
-  if (dn_status st = wgrad_g(c, dprm, W_C3, P.ne2, c.V(p.dsg, 4), c.V(p.h, 48), H, W)) return st;
-  if (dn_status st = dgrad_g(c, P.ne2, c.V(p.dsg, 4), H, W, 48, EPI_MASK, c.V(p.h, 48),
-                             c.V(p.dh, 48)))
-    return st;
+  if (dn_status st = wgrad_g(c, dprm, P.ne2)) return st;
+  if (dn_status st = dgrad_g(c, P.ne2)) return st;
   {
     float* slab = ws + p.slab;
     const long n = 48L * C * 9 + 48;
     const int st = enc0_wgrad_splits(N, H, W);
-    IU_RUN(c, fork());
-    IU_RUN(c, launch_wgrad_c3_thin(ws + p.dh, 48, ws + p.xin, N, C, H, W, slab, n, C, 0, 1, st,
-                                   s2));
-    IU_RUN(c, launch_reduce(slab, n, st, n, dprm + P.ne0.w, s2));
+    IU_TRY(side_fork(c.side, s));
+    IU_TRY(launch_wgrad_c3_thin(ws + p.dh, 48, ws + p.xin, N, C, H, W, slab, n, C, 0, 1, st, s2));
+    IU_TRY(launch_reduce(slab, n, st, n, dprm + P.ne0.w, s2));
   }
-  if (side) {  // the caller's stream continues after every weight gradient
-    IU_RUN(c, hipEventRecord(side->join, s2));
-    IU_RUN(c, hipStreamWaitEvent(s, side->join, 0));
+  if (c.side) {  // the caller's stream continues after every weight gradient
+    IU_TRY(hipEventRecord(c.side->join, s2));
+    IU_TRY(hipStreamWaitEvent(s, c.side->join, 0));
   }
   return DN_OK;
 }
@@ -949,22 +855,16 @@ dn_status iunet_backward(const IPlan& p, const float* prm, const float* dy, floa
   const StreamDeviceGuard device_guard(s);
   if (prec != DN_PREC_FP32 && prec != DN_PREC_FP32_X6) return DN_ERR_ARG;
   // The weight gradients (and their slab reductions) run on a side stream beside the
-  // data-gradient chain (DN_BWD_STREAMS=0 or per-op profiling: one stream).  Each is forked after
+  // data-gradient chain (DN_BWD_STREAMS=0 or launch profiling: one stream).  Each is forked after
   // the launch that produced its output gradient; every buffer one reads (the forward's
   // activations, dz2 / dz1 / dr / dzf of a block, dzj[j], dps[k], dza[i], dzfin, dsg, dh once
   // written) is not rewritten later in the pass, and only they use the slab.  Joined at the end.
-  SideStream* side = bwd_two_streams() && !prof_on() && !g_prof.on ? side_stream(s) : nullptr;
-  PackBatch pb;
-  long next = 0;
-  Ctx c{p, prm, ws, s, prec};
-  if (side) { c.s2 = side->st; c.fork = side->fork; }
-  c.pb = &pb; c.next = &next; c.dry = true;
-  if (dn_status st = backward_body(c, dy, dprm, side)) return st;
-  IU_TRY(pack_flush(pb, s));
-  next = 0; c.dry = false;
-  if (dn_status st = backward_body(c, dy, dprm, side)) return st;
-  g_prof.flush("iunet backward");
-  return DN_OK;
+  SideStream* side = bwd_two_streams() && !prof_on() ? side_stream(s) : nullptr;
+  IRoutes R;
+  if (dn_status st = iunet_bwd_routes(p, prec, R)) return st;
+  const Ctx c{p, R, prm, ws, s, prec, side};
+  if (dn_status st = pack_images(c, true)) return st;
+  return backward_body(c, dy, dprm);
 }
 
 }  // namespace dn

@@ -8,12 +8,15 @@
 namespace dn {
 
 // offsets (floats) of one layer's tensors in the flat parameter buffer
-struct IConv { long w = -1, b = -1; int cout = 0, cin = 0, k = 3; };
+// (idx: the conv's position in state_dict order = its entry in IPlan::site)
+struct IConv { long w = -1, b = -1; int cout = 0, cin = 0, k = 3, idx = -1; };
 struct IGN { long g = -1, b = -1; int C = 0, G = 0; };
 struct IRdb { IConv conv[4]; IConv lff; int C = 0; };
 struct IRes { IConv c1, c2; IGN n1, n2; int C = 0; };
 struct ILevel { IConv conv; IRdb rdb; IRes res; };
 struct IUp { IConv ps, fuse; IRdb rdb; IRes res; int in = 0, out = 0; };
+
+constexpr int kIConvs = 78;  // 2 (noise estimator) + 4 x 8 + 7 (bottle) + 4 x 9 + 1 (final)
 
 struct IParams {
   int C = 1, OC = 1, nf = 48;
@@ -38,8 +41,27 @@ struct IBlockBufs {
   long dF = 0, dr = 0, dz2 = 0, dg1 = 0, dz1 = 0, dzj[4] = {0, 0, 0, 0}, dzf = 0;
 };
 
+// a strided NHWC view of a workspace buffer: offset (floats; < 0: none), pixel stride, channel offset
+struct IView { long o = -1; int stride = 0, off = 0; };
+
+// Where one convolution sits in the dataflow: what its forward, data-gradient and weight-gradient
+// launches read and write.  The passes look a conv's site up by IConv::idx; the weight gradient's
+// x operand IS the forward input `in`.
+struct ISite {
+  IConv L;
+  int lvl = 0;             // runs at (H >> lvl) x (W >> lvl); conv_ps: one level below its block
+  IView in;                // forward input
+  IView out, aux;          // forward on the generic kernels (out.o < 0: a thin kernel, launched
+  int epi = 0, layout = 0; //   by the pass itself); aux = EPI_BIAS_ADD's residual
+  int wmode = -1;          // weight gradient W_C3 / W_C1 on the blocked kernels (-1: thin, as above)
+  IView g;                 // dL/d(conv output): read by the weight and the data gradient
+  int nout = 0, depi = 0;  // data gradient of the first nout input channels (0: none) into dx;
+  IView daux, dx;          //   daux = EPI_MASK's saved activation / EPI_BIAS_ADD's residual
+};
+
 struct IPlan {
   IParams P;
+  ISite site[kIConvs];
   int N = 0, H = 0, W = 0;
   bool with_bwd = false;
   long x0 = 0, h = 0;                 // [x, sigma, 0] (stride 4); noise-estimator hidden (48)
@@ -52,7 +74,7 @@ struct IPlan {
   long cf = 0;                        // final concat [x_up3 (24) | x (C) | 0]  stride 28
   long sc = 0, sh = 0;                // GN scale / shift scratch [N * 384]
   long gpart = 0;                     // GN partial sums (doubles)
-  long pack = 0, pack_floats = 0;     // packed-weight arena (one slot per conv of a pass)
+  long pack = 0, pack_floats = 0;     // packed-weight arena (a pass's weight images, one per site)
   // gradients
   long dzfin = 0, dcc[4] = {0, 0, 0, 0}, dps[4] = {0, 0, 0, 0}, dxu[3] = {0, 0, 0}, dxb = 0, dpool = 0;
   long dza[4] = {0, 0, 0, 0}, dsg = 0, dh = 0, ca = 0, cb = 0, ccf = 0;

@@ -118,6 +118,24 @@ def test_workspace_size_validation(N, H, W, bwd, ok):
         assert "multiple" in _lib.last_error() or "N >= 1" in _lib.last_error()
 
 
+@pytest.mark.parametrize("C,N,H,W,bwd,nbytes", [
+    (1, 1, 32, 48, 0, 178934272), (1, 1, 32, 48, 1, 213083392), (3, 2, 32, 128, 1, 307589376),
+    (1, 8, 128, 128, 1, 1917142272), (1, 64, 128, 128, 1, 13460009216),
+    (1, 64, 256, 256, 0, 21721835520),
+])
+def test_iunet_workspace_size_unchanged(C, N, H, W, bwd, nbytes):
+    """The ImprovedUNet workspace (activations, gradients, the packed-weight arena summed over the
+    plan's conv sites, the weight-gradient slab as the max over them) is byte for byte what the
+    executor asked for when it sized the arena and the slab from hand-written walks of the
+    network: the constants are that build's answers."""
+    from image_denoising_amd import _lib
+
+    cfg = _lib.cfg(C, C, 48)
+    n = ctypes.c_size_t()
+    assert _lib.lib().dn_iunet_workspace_size(ctypes.byref(cfg), N, H, W, bwd, ctypes.byref(n)) == 0
+    assert n.value == nbytes
+
+
 def test_unsupported_config_is_an_error_not_a_fallback():
     from image_denoising_amd import _lib
 
