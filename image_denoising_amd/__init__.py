@@ -10,6 +10,7 @@ from .finetune import FinetuneTrainer  # noqa: F401
 from .improved_unet import ImprovedUNet  # noqa: F401
 from .n2n import (AugmentNoise, generate_mask_pair, generate_subimages,  # noqa: F401
                   n2n_loss, n2n_subsample)
+from .resnet import RESNET  # noqa: F401
 from .optim import FlatAdam, lr_at_epoch  # noqa: F401
 from .trainer import N2NTrainer, StructureTrainer  # noqa: F401
 from .util import Structure_loss  # noqa: F401

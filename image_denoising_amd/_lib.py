@@ -66,6 +66,17 @@ SIGNATURES = {
                                        POINTER(c_int64)]),
     "dn_unet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
                                       POINTER(c_int64), c_int, POINTER(c_int)]),
+    "dn_resnet_param_count": (c_int, [POINTER(DnCfg), POINTER(c_size_t)]),
+    "dn_resnet_param_info": (c_int, [POINTER(DnCfg), c_int, POINTER(c_size_t), POINTER(c_size_t),
+                                     POINTER(c_size_t)]),
+    "dn_resnet_workspace_size": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
+                                         POINTER(c_size_t)]),
+    "dn_resnet_forward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
+                                       c_size_t, c_int, c_void_p]),
+    "dn_resnet_backward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, _F, c_int, c_int, c_int,
+                                        c_void_p, c_size_t, c_int, c_void_p]),
+    "dn_resnet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
+                                        POINTER(c_int64), c_int, POINTER(c_int)]),
     "dn_n2n_subsample": (c_int, [_F, c_int, c_int, c_int, c_int, _U8, c_uint64, c_uint64, c_uint64,
                                  _F, _F, _U8, c_void_p]),
     "dn_n2n_masks": (c_int, [_U8, c_int64, _U8, _U8, c_void_p]),

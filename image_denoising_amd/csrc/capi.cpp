@@ -5,6 +5,7 @@
 #include <string>
 
 #include "iunet.h"
+#include "resnet.h"
 #include "unet.h"
 
 using namespace dn;
@@ -294,6 +295,120 @@ dn_status dn_unet_debug_buffers(const dn_unet_cfg* cfg, int N, int H, int W, int
     for (int l = 1; l <= 4; ++l) add(p.g_db[l], 2 * nf, l);
     for (int l = 1; l <= 4; ++l) add(p.g_a[l], nf, l);
     add(p.g_a6, nf, 5); add(p.g_p5, nf, 5); add(p.g_a0, nf, 0); add(p.g_a1, nf, 0);
+  }
+  *n_entries = n;
+  return DN_OK;
+  DN_GUARD_END
+}
+
+// ---- RESNET -------------------------------------------------------------------------
+dn_status dn_resnet_param_count(const dn_unet_cfg* cfg, size_t* count) {
+  DN_GUARD_BEGIN
+  if (!cfg || !count) return fail(DN_ERR_ARG, "null argument");
+  ResParamLayout P;
+  std::string err;
+  if (!res_build_params(*cfg, P, err)) return fail(DN_ERR_ARG, err);
+  *count = (size_t)P.total;
+  return DN_OK;
+  DN_GUARD_END
+}
+
+dn_status dn_resnet_param_info(const dn_unet_cfg* cfg, int index, size_t* w_off, size_t* w_count,
+                               size_t* b_count) {
+  DN_GUARD_BEGIN
+  if (!cfg || !w_off || !w_count || !b_count) return fail(DN_ERR_ARG, "null argument");
+  ResParamLayout P;
+  std::string err;
+  if (!res_build_params(*cfg, P, err)) return fail(DN_ERR_ARG, err);
+  if (index < 0 || index >= R_NL) return fail(DN_ERR_ARG, "layer index out of range");
+  *w_off = (size_t)P.L[index].woff;
+  *w_count = (size_t)P.L[index].wcount;
+  *b_count = (size_t)P.L[index].cout;
+  return DN_OK;
+  DN_GUARD_END
+}
+
+dn_status dn_resnet_workspace_size(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
+                                   size_t* bytes) {
+  DN_GUARD_BEGIN
+  if (!cfg || !bytes) return fail(DN_ERR_ARG, "null argument");
+  ResPlan p;
+  std::string err;
+  if (!res_build_plan(*cfg, N, H, W, with_backward != 0, p, err)) return fail(DN_ERR_ARG, err);
+  *bytes = (size_t)p.total_floats * sizeof(float);
+  return DN_OK;
+  DN_GUARD_END
+}
+
+dn_status dn_resnet_forward_prec(const dn_unet_cfg* cfg, const float* params, const float* x,
+                                 float* y, int N, int H, int W, void* ws, size_t ws_bytes,
+                                 int precision, void* stream) {
+  DN_GUARD_BEGIN
+  if (precision != DN_PREC_FP32 && precision != DN_PREC_FP32_X6)
+    return fail(DN_ERR_ARG, "RESNET precision must be DN_PREC_FP32 or DN_PREC_FP32_X6");
+  if (!cfg || !params || !x || !y || !ws) return fail(DN_ERR_ARG, "null argument");
+  ResPlan p;
+  std::string err;
+  // the workspace's size decides the plan, as in dn_unet_forward_prec
+  if (!res_build_plan(*cfg, N, H, W, true, p, err)) return fail(DN_ERR_ARG, err);
+  if (ws_bytes < (size_t)p.total_floats * sizeof(float) &&
+      !res_build_plan(*cfg, N, H, W, false, p, err))
+    return fail(DN_ERR_ARG, err);
+  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
+    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_resnet_workspace_size()");
+  return resnet_forward(p, params, x, y, static_cast<float*>(ws), (hipStream_t)stream, precision);
+  DN_GUARD_END
+}
+
+dn_status dn_resnet_backward_prec(const dn_unet_cfg* cfg, const float* params, const float* dy,
+                                  float* dparams, float* dx, int N, int H, int W, void* ws,
+                                  size_t ws_bytes, int precision, void* stream) {
+  DN_GUARD_BEGIN
+  if (precision != DN_PREC_FP32 && precision != DN_PREC_FP32_X6)
+    return fail(DN_ERR_ARG, "RESNET precision must be DN_PREC_FP32 or DN_PREC_FP32_X6");
+  if (!cfg || !params || !dy || !dparams || !ws) return fail(DN_ERR_ARG, "null argument");
+  ResPlan p;
+  std::string err;
+  if (!res_build_plan(*cfg, N, H, W, true, p, err)) return fail(DN_ERR_ARG, err);
+  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
+    return fail(DN_ERR_WORKSPACE,
+                "workspace smaller than dn_resnet_workspace_size(with_backward=1)");
+  return resnet_backward(p, params, dy, dparams, dx, static_cast<float*>(ws), (hipStream_t)stream,
+                         precision);
+  DN_GUARD_END
+}
+
+/* order: c1 a0 c2 c3 c4 c5 a5 d2a d3a d4a d5a d1a d1b | na nb g_na g_d1b g_d1a g_c1 g_c2..g_c5
+   g_d2a..g_d5a g_a1..g_a4 g_a5 g_a0 */
+dn_status dn_resnet_debug_buffers(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
+                                  int64_t* desc, int max_entries, int* n_entries) {
+  DN_GUARD_BEGIN
+  if (!cfg || !desc || !n_entries) return fail(DN_ERR_ARG, "null argument");
+  ResPlan p;
+  std::string err;
+  if (!res_build_plan(*cfg, N, H, W, with_backward != 0, p, err)) return fail(DN_ERR_ARG, err);
+  int n = 0;
+  auto add = [&](long off, int stride) {
+    if (n < max_entries) {
+      desc[3 * n] = off;
+      desc[3 * n + 1] = stride;
+      desc[3 * n + 2] = 0;
+    }
+    ++n;
+  };
+  const int nf = p.nf;
+  add(p.c1, p.c1s); add(p.a0, nf);
+  for (int k = 2; k <= 5; ++k) add(p.c[k], p.cs[k]);
+  add(p.a5, nf);
+  for (int k = 2; k <= 5; ++k) add(p.da[k], 2 * nf);
+  add(p.d1a, 96); add(p.d1b, 96);
+  if (with_backward) {
+    add(p.na, 96); add(p.nb, 96);
+    add(p.g_na, 96); add(p.g_d1b, 96); add(p.g_d1a, 96); add(p.g_c1, 2 * nf);
+    for (int k = 2; k <= 5; ++k) add(p.g_c[k], p.cs[k]);
+    for (int k = 2; k <= 5; ++k) add(p.g_da[k], 2 * nf);
+    for (int j = 1; j <= 4; ++j) add(p.g_a[j], nf);
+    add(p.g_a5, nf); add(p.g_a0, nf);
   }
   *n_entries = n;
   return DN_OK;

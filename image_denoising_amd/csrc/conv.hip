@@ -74,7 +74,9 @@ __device__ __forceinline__ void glds16(const float* g, float* l) {
 // values).  lds must hold HEAD_LW floats and be free.  k_fwd<..., HEAD> keeps its own inline copy
 // of the PRE_ACT form: through this function its 168-register budget (3 workgroups per CU)
 // spills.
-template <int MT, bool PRE_ACT>
+// RES: the network input hd.res (NCHW, oc channels) added to nin_c's output (the RESNET's global
+// residual); without it the instantiation is the UNet's, unchanged.
+template <int MT, bool PRE_ACT, bool RES = false>
 __device__ __forceinline__ void head_tail(const FwdArgs& a, const HeadArgs& hd,
                                           f32x4 (&acc)[MT][6], float* lds, int ty0, int tx0,
                                           int n) {
@@ -169,7 +171,11 @@ __device__ __forceinline__ void head_tail(const FwdArgs& a, const HeadArgs& hd,
         }
         t += __shfl_xor(t, 16);
         t += __shfl_xor(t, 32);
-        if (lg == 0 && ok) hd.y[(((long)n * hd.oc + o) * a.OH + gy) * a.OW + gx] = t + hd.bc[o];
+        if (lg == 0 && ok) {
+          const long yi = (((long)n * hd.oc + o) * a.OH + gy) * a.OW + gx;
+          if constexpr (RES) hd.y[yi] = (t + hd.bc[o]) + hd.res[yi];
+          else hd.y[yi] = t + hd.bc[o];
+        }
       }
     }
 }
@@ -397,7 +403,7 @@ __global__ __launch_bounds__(256, (GATHER == G_C3 && NT == 6) ? 3 : 2) void k_fw
 
 // The same head on an already activated dec_conv1b output (hd.d1b ignored; a.in = d1b NHWC,
 // stride 96): the head of a forward whose dec_conv1b ran on another kernel (bf16x6).
-template <int MT>
+template <int MT, bool RES = false>
 __global__ __launch_bounds__(256, 2) void k_nin_head(FwdArgs a, HeadArgs hd) {
   __shared__ __attribute__((aligned(16))) float lds[HEAD_LW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -417,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void k_nin_head(FwdArgs a, HeadArgs hd) {
       acc[m][q] = f32x4{v.x, v.y, v.z, v.w};
     }
   }
-  head_tail<MT, false>(a, hd, acc, lds, ty0, tx0, n);
+  head_tail<MT, false, RES>(a, hd, acc, lds, ty0, tx0, n);
 }
 
 // Backward of the fused head (see HeadBwdArgs).  A workgroup loads the two transposed 1x1
@@ -1064,7 +1070,7 @@ static hipError_t run_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s) {
 }
 
 hipError_t launch_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s) {
-  if (a.NOUT != 96 || h.oc < 1) return hipErrorInvalidValue;
+  if (a.NOUT != 96 || h.oc < 1 || h.res) return hipErrorInvalidValue;  // (residual: k_nin_head)
   const long tiles = (long)a.N * ((a.OH + 15) / 16) * ((a.OW + 15) / 16);
   return tiles < 1024 ? run_head<1>(a, h, s) : run_head<4>(a, h, s);
 }
@@ -1074,7 +1080,9 @@ hipError_t launch_nin_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s) {
   const long tiles = (long)a.N * ((a.OH + 15) / 16) * ((a.OW + 15) / 16);
   const int mt = tiles < 1024 ? 1 : 2;
   const dim3 grid(((a.OW + 15) / 16) * ((a.OH + 4 * mt - 1) / (4 * mt)), a.N, 1);
-  if (mt == 1) hipLaunchKernelGGL((k_nin_head<1>), grid, dim3(256), 0, s, a, h);
+  if (h.res && mt == 1) hipLaunchKernelGGL((k_nin_head<1, true>), grid, dim3(256), 0, s, a, h);
+  else if (h.res) hipLaunchKernelGGL((k_nin_head<2, true>), grid, dim3(256), 0, s, a, h);
+  else if (mt == 1) hipLaunchKernelGGL((k_nin_head<1>), grid, dim3(256), 0, s, a, h);
   else hipLaunchKernelGGL((k_nin_head<2>), grid, dim3(256), 0, s, a, h);
   return hipGetLastError();
 }

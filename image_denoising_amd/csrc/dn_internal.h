@@ -125,6 +125,9 @@ struct HeadArgs {
   // the input is a pair image (launch_fwd_x6_sel): output pixel (i, 2j + s) of the head goes to
   // y's pixel pair[rd[n][i][j]][s] of cell (i, j), y itself [N, oc, 2 * OH, OW]
   const unsigned char* rd;
+  // nullable: the network input (NCHW [N, oc, H, W], y's layout) added to nin_c's output -- the
+  // RESNET's global residual (launch_nin_head, launch_nin_head_x6 without rd / bf16)
+  const float* res;
 };
 // Backward of the head: g_nb = leaky'(nb) * (Wc^T dy), g_na = leaky'(na) * (Wb^T g_nb),
 // g_d1b = leaky'(d1b) * (Wa^T g_na) over npx pixels (all NHWC stride 96, dy stride dy_stride)
@@ -311,10 +314,11 @@ hipError_t launch_enc0_wgrad(const float* g, int g_stride, const float* x, int N
                              int W, float* slab, int splits, float* dwb, hipStream_t s,
                              RedBatch* rb = nullptr);
 // dL/dx (NCHW) of the network input from enc_conv0's (48 ch) and dec_conv1a's (96 ch, input
-// channels [c1_base, c1_base + C) of c1_total) pre-activation gradients
+// channels [c1_base, c1_base + C) of c1_total) pre-activation gradients; res (nullable, NCHW as
+// dx): added to it -- the gradient through the RESNET's global residual (dL/dy, out_nc == C)
 hipError_t launch_dgrad_input(const float* g0, const float* w0, const float* g1, const float* w1,
                               int c1_total, int c1_base, int N, int C, int H, int W, float* dx,
-                              hipStream_t s);
+                              hipStream_t s, const float* res = nullptr);
 constexpr int EVAL_PARTS = 1024;
 hipError_t launch_u8_to_unit(const uint8_t* x, long n, float* y, hipStream_t s);
 hipError_t launch_tile_extract(const uint8_t* img, int C, int H, int W, int ps, int stride,
@@ -340,6 +344,9 @@ hipError_t launch_wgrad_thin(const float* g, int g_stride, int cout, const float
                              float* slab, int splits, float* dwb, hipStream_t s,
                              RedBatch* rb = nullptr);
 hipError_t launch_accumulate(float* dst, const float* src, long n, hipStream_t s);
+// out[p][c] = a[p * as + aoff + c] + b[p][c], c < C (multiples of 4; out, b compact [npx][C])
+hipError_t launch_add_slice(const float* a, int as, int aoff, const float* b, int C, long npx,
+                            float* out, hipStream_t s);
 hipError_t launch_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s);
 // nin_a -> nin_b -> nin_c on an activated dec_conv1b output (a.in, a.K = 96); h.d1b unused
 hipError_t launch_nin_head(const FwdArgs& a, const HeadArgs& h, hipStream_t s);

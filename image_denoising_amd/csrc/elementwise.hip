@@ -650,6 +650,32 @@ hipError_t launch_accumulate(float* dst, const float* src, long n, hipStream_t s
   return hipGetLastError();
 }
 
+// out[p][c] = a[p * as + aoff + c] + b[p][c] for c < C (C, as, aoff multiples of 4; out and b
+// compact [npx][C]): the RESNET backward's sum of an encoder activation's two gradients, the skip
+// slice of a concat gradient and the next encoder conv's data gradient.  One float4 per thread,
+// grid-stride; every index is below npx * C / 4.
+__global__ __launch_bounds__(256) void k_add_slice(const float* __restrict__ a, int as, int aoff,
+                                                   const float* __restrict__ b, int C, long npx,
+                                                   float* __restrict__ out) {
+  const int cq = C >> 2;
+  const long n4 = npx * cq;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const long p = i / cq;
+    const int c = (int)(i - p * cq) * 4;
+    const float4 u = *reinterpret_cast<const float4*>(a + p * as + aoff + c);
+    const float4 v = reinterpret_cast<const float4*>(b)[i];
+    reinterpret_cast<float4*>(out)[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+  }
+}
+
+hipError_t launch_add_slice(const float* a, int as, int aoff, const float* b, int C, long npx,
+                            float* out, hipStream_t s) {
+  if (C < 4 || ((C | as | aoff) & 3) || aoff + C > as || npx < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_add_slice, dim3(grid_for(npx * (C >> 2), 256, 8192)), dim3(256), 0, s, a, as,
+                     aoff, b, C, npx, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float w1,
                        float b2, float w2, float step_size, float bc2s, float eps, float gscale,
                        hipStream_t s) {

@@ -292,14 +292,16 @@ hipError_t launch_enc0_wgrad(const float* g, int g_stride, const float* x, int N
 // out-of-image taps skipped.  One output pixel per thread, all C channels; the weights of the
 // C input channels live transposed in LDS ([c][t][co], broadcast float4 reads); the 144
 // gradient channels of the 9 neighbours come through L1/L2 as float4 rows.  Fixed summation
-// order (taps, then enc_conv0's channels, then dec_conv1a's): deterministic.
-template <int C>
+// order (taps, then enc_conv0's channels, then dec_conv1a's): deterministic.  RES: dx += res
+// (NCHW as dx), the gradient arriving through the RESNET's global residual.
+template <int C, bool RES = false>
 __global__ __launch_bounds__(256) void k_dgrad_input(const float* __restrict__ g0,
                                                      const float* __restrict__ w0,
                                                      const float* __restrict__ g1,
                                                      const float* __restrict__ w1, int c1_total,
                                                      int c1_base, int N, int H, int W,
-                                                     float* __restrict__ dx) {
+                                                     float* __restrict__ dx,
+                                                     const float* __restrict__ res) {
   constexpr int C0 = 48, C1 = 96;
   __shared__ __attribute__((aligned(16))) float wl[C][9][C0 + C1];
   for (int e = threadIdx.x; e < C * 9 * (C0 + C1); e += 256) {
@@ -337,17 +339,26 @@ __global__ __launch_bounds__(256) void k_dgrad_input(const float* __restrict__ g
     }
   }
 #pragma unroll
-  for (int c = 0; c < C; ++c) dx[(n * C + c) * hw + r] = acc[c];
+  for (int c = 0; c < C; ++c) {
+    if constexpr (RES) dx[(n * C + c) * hw + r] = acc[c] + res[(n * C + c) * hw + r];
+    else dx[(n * C + c) * hw + r] = acc[c];
+  }
 }
 
 hipError_t launch_dgrad_input(const float* g0, const float* w0, const float* g1, const float* w1,
                               int c1_total, int c1_base, int N, int C, int H, int W, float* dx,
-                              hipStream_t s) {
+                              hipStream_t s, const float* res) {
   const long total = (long)N * H * W;
   const dim3 grid((unsigned)((total + 255) / 256));
-#define DN_DGI(CC)                                                                           \
-  hipLaunchKernelGGL(k_dgrad_input<CC>, grid, dim3(256), 0, s, g0, w0, g1, w1, c1_total,    \
-                     c1_base, N, H, W, dx)
+#define DN_DGI(CC)                                                                             \
+  do {                                                                                         \
+    if (res)                                                                                   \
+      hipLaunchKernelGGL((k_dgrad_input<CC, true>), grid, dim3(256), 0, s, g0, w0, g1, w1,     \
+                         c1_total, c1_base, N, H, W, dx, res);                                 \
+    else                                                                                       \
+      hipLaunchKernelGGL((k_dgrad_input<CC, false>), grid, dim3(256), 0, s, g0, w0, g1, w1,    \
+                         c1_total, c1_base, N, H, W, dx, res);                                 \
+  } while (0)
   if (C == 1) DN_DGI(1);
   else if (C == 2) DN_DGI(2);
   else if (C == 3) DN_DGI(3);

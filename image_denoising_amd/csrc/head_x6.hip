@@ -27,10 +27,13 @@ namespace dn {
 // leading planes (the weights rounded to bf16), one MFMA per block chained in fp32
 // IBF (with B1): the input activation is stored as bf16 (FwdArgs::in_bf16), 8 bytes per lane and
 // 4 channels, taken as the operand without conversion
-template <bool SAVE, bool PAIR, bool B1 = false, bool IBF = false>
+// RES: the network input hd.res (NCHW, oc channels, y's layout) added to nin_c's output in the
+// epilogue (the RESNET's global residual)
+template <bool SAVE, bool PAIR, bool B1 = false, bool IBF = false, bool RES = false>
 __global__ __launch_bounds__(512, 1) void k_nin_head_x6(FwdArgs a, HeadArgs hd, const __bf16* wimg,
                                                       int nwt) {
   static_assert(!IBF || B1, "bf16 input only in the plain-bf16 head");
+  static_assert(!RES || (!PAIR && !B1), "the residual head is the full-image split-product head");
   __shared__ __attribute__((aligned(16))) __bf16 lw[2 * X6_HEAD_BF];
   __shared__ __attribute__((aligned(16))) float lb[2 * 96 + X6_HEAD_OCMAX * 97];  // ba|bb|wc|bc
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -182,7 +185,14 @@ __global__ __launch_bounds__(512, 1) void k_nin_head_x6(FwdArgs a, HeadArgs hd, 
       const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
           hd.y + (((long)n * hd.oc + o) * YR * a.OH + YR * gy) * a.OW, (short)0, YR * a.OW * 4,
           0x00020000);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t + lbc[o]), ry, yoff, 0, 0);
+      float yv = t + lbc[o];
+      if constexpr (RES) {  // (out-of-range lanes read zero and drop their store)
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(hd.res) + (((long)n * hd.oc + o) * a.OH + gy) * a.OW, (short)0,
+            a.OW * 4, 0x00020000);
+        yv += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, yoff, 0, 0));
+      }
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yv), ry, yoff, 0, 0);
     }
   };
   int wt = blockIdx.x * 8 + wave;
@@ -357,7 +367,12 @@ hipError_t launch_nin_head_x6(const FwdArgs& a, const HeadArgs& h, const void* w
   const dim3 grid((unsigned)blocks), block(512);
   const bool save = h.na && h.nb;
   if (save && h.rd) return hipErrorInvalidValue;  // the pair pass saves nothing
-  if (h.rd) hipLaunchKernelGGL((k_nin_head_x6<false, true>), grid, block, 0, s, a, h, w, (int)nwt);
+  if (h.res && (h.rd || bf16)) return hipErrorInvalidValue;
+  if (h.res && save)
+    hipLaunchKernelGGL((k_nin_head_x6<true, false, false, false, true>), grid, block, 0, s, a, h, w, (int)nwt);
+  else if (h.res)
+    hipLaunchKernelGGL((k_nin_head_x6<false, false, false, false, true>), grid, block, 0, s, a, h, w, (int)nwt);
+  else if (h.rd) hipLaunchKernelGGL((k_nin_head_x6<false, true>), grid, block, 0, s, a, h, w, (int)nwt);
   else if (save) hipLaunchKernelGGL((k_nin_head_x6<true, false>), grid, block, 0, s, a, h, w, (int)nwt);
   else if (bf16 && a.in_bf16)
     hipLaunchKernelGGL((k_nin_head_x6<false, false, true, true>), grid, block, 0, s, a, h, w, (int)nwt);

@@ -117,9 +117,12 @@ class DenoisePatchDataset(torch.utils.data.Dataset):
 
 
 def build_base_model(arch: str, n_channel: int = 1, n_feature: int = 48) -> nn.Module:
-    """finetune.py:180-196 (only the UNet base is built on the HIP path)."""
+    """finetune.py:180-196: the base network by name."""
     if arch == "UNet":
         return UNet(in_nc=n_channel, out_nc=n_channel, n_feature=n_feature)
+    if arch == "RESNET":
+        from .resnet import RESNET
+        return RESNET(in_nc=n_channel, out_nc=n_channel, n_feature=n_feature)
     if arch == "UNetImproved":
         from .improved_unet import ImprovedUNet
         return ImprovedUNet(in_nc=n_channel, out_nc=n_channel, n_feature=n_feature)

@@ -64,7 +64,8 @@ const char* dn_version(void);
    `float* dx` argument after `dparams` (revision 2 had no dx: an old caller's arguments would
    be shifted, so check dn_abi_version() == DN_ABI_VERSION before binding).  Revision 4
    (library 0.4.x): dn_unet_backward_split added.  Revision 5 (library 0.5.x):
-   dn_unet_pack_weights / dn_unet_forward_prepacked added (existing signatures unchanged). */
+   dn_unet_pack_weights / dn_unet_forward_prepacked added (existing signatures unchanged).  The
+   dn_resnet_* symbols were added within revision 5 (no existing signature changed). */
 #define DN_ABI_VERSION 5
 int dn_abi_version(void);
 /* copies the last error message of this thread into buf (NUL-terminated); returns its length */
@@ -474,6 +475,36 @@ dn_status dn_conv2d_backward_weight_blocked(const float* g, int g_stride, int g_
                                             const float* x, int x_stride, int x_off, int N, int H,
                                             int W, int Cin, int Cout, int ksize, int bias,
                                             int precision, float* dwb, void* slab, void* stream);
+
+/* ---- RESNET (arch_unet.py:263-409) ------------------------------------------------ */
+/* The UNet's layers without pooling or upsampling: every layer runs at the input resolution, any
+   H, W >= 1, and the network returns nin_c(...) + x.  Same conventions as the dn_unet_* calls
+   (flat parameters in state_dict order, NCHW x / y / dy / dx, caller-owned workspace; a workspace
+   sized with_backward=1 makes the forward save what the backward reads).  21 layers: enc_conv0..6,
+   up5.deconv, dec_conv5a/b .. dec_conv2a/b, dec_conv1a/b, nin_a/b/c.  up5.deconv belongs to the
+   checkpoint but is never used: dn_resnet_backward_prec writes exact zeros over its range of
+   dparams.  Deviation from torch: the residual needs out_nc == in_nc (torch would broadcast a
+   one-channel side); any other pair is DN_ERR_ARG.  precision: DN_PREC_FP32 or DN_PREC_FP32_X6
+   (DN_PREC_BF16: DN_ERR_ARG). */
+dn_status dn_resnet_param_count(const dn_unet_cfg* cfg, size_t* count);
+dn_status dn_resnet_param_info(const dn_unet_cfg* cfg, int index, size_t* w_off, size_t* w_count,
+                               size_t* b_count);
+dn_status dn_resnet_workspace_size(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
+                                   size_t* bytes);
+dn_status dn_resnet_forward_prec(const dn_unet_cfg* cfg, const float* params, const float* x,
+                                 float* y, int N, int H, int W, void* ws, size_t ws_bytes,
+                                 int precision, void* stream);
+/* dparams is overwritten; dx (nullable) = dL/dx = dy + the gradients through enc_conv0 and
+   dec_conv1a's image channels */
+dn_status dn_resnet_backward_prec(const dn_unet_cfg* cfg, const float* params, const float* dy,
+                                  float* dparams, float* dx, int N, int H, int W, void* ws,
+                                  size_t ws_bytes, int precision, void* stream);
+/* Debug/introspection: (offset_floats, channel_stride, level = 0) of the NHWC buffers
+   c1 a0 c2 c3 c4 c5 a5 d2a d3a d4a d5a d1a d1b (c1 = [d2b | x | pad], c2..c4 = [d{k+1}b |
+   a{k-1}], c5 = [a6 | a4]); with_backward adds na nb (saved only for a backward) g_na g_d1b
+   g_d1a g_c1 g_c2..g_c5 g_d2a..g_d5a g_a1..g_a4 g_a5 g_a0 */
+dn_status dn_resnet_debug_buffers(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
+                                  int64_t* desc, int max_entries, int* n_entries);
 
 #ifdef __cplusplus
 }
