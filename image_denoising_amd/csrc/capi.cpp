@@ -1,6 +1,8 @@
 // extern "C" boundary of libdenoise_hip.so (declared in include/denoise_hip.h).
 // Validates arguments, maps failures to dn_status + a thread-local message, never throws.
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -497,6 +499,20 @@ dn_status dn_structure_loss(const float* pred, const float* pred2, const float* 
                     "dn_structure_loss");
 }
 
+// The double a caller wrote before the ABI narrowed it to fp32: the shortest decimal that rounds
+// to x.  torch.optim.Adam keeps lr and the betas as Python doubles and forms 1 - beta, beta^step
+// and lr / bc1 from those.  (double)0.999f is 0.99900001287..., and 1 - beta2 formed from it is
+// 1.3e-5 (relative) away from torch's, and exp_avg_sq with it.
+static double as_written(float x) {
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    std::snprintf(buf, sizeof buf, "%.*g", prec, (double)x);
+    const double d = std::strtod(buf, nullptr);
+    if ((float)d == x) return d;
+  }
+  return (double)x;
+}
+
 dn_status dn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                        float lr, float beta1, float beta2, float eps, int64_t step,
                        float grad_scale, void* stream) {
@@ -504,14 +520,15 @@ dn_status dn_adam_step(float* param, const float* grad, float* exp_avg, float* e
   if (n == 0) return DN_OK;
   if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(DN_ERR_ARG, "null argument");
   // scalars exactly as torch/optim/adam.py _single_tensor_adam computes them (python floats)
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  const double step_size = (double)lr / bc1;
+  const double b1 = as_written(beta1), b2 = as_written(beta2);
+  const double bc1 = 1.0 - std::pow(b1, (double)step);
+  const double bc2 = 1.0 - std::pow(b2, (double)step);
+  const double step_size = as_written(lr) / bc1;
   const double bc2s = std::sqrt(bc2);
   const OpTimer timer((hipStream_t)stream, "adam", 0);
-  return hip_status(launch_adam(param, grad, exp_avg, exp_avg_sq, n, (float)(1.0 - (double)beta1),
-                                beta2, (float)(1.0 - (double)beta2), (float)step_size,
-                                (float)bc2s, eps, grad_scale, (hipStream_t)stream),
+  return hip_status(launch_adam(param, grad, exp_avg, exp_avg_sq, n, (float)(1.0 - b1), beta2,
+                                (float)(1.0 - b2), (float)step_size, (float)bc2s, eps, grad_scale,
+                                (hipStream_t)stream),
                     "dn_adam_step");
 }
 

@@ -641,12 +641,10 @@ hipError_t launch_accumulate(float* dst, const float* src, long n, hipStream_t s
   long blocks = ((vec ? n / 4 : n) + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  if (vec) {
+  if (vec)
     hipLaunchKernelGGL(k_accumulate, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, n);
-  } else {  // unaligned views: the scalar tail loop covers everything
-    hipLaunchKernelGGL(k_accumulate, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, 0L);
+  else  // unaligned views: the scalar loop covers everything
     hipLaunchKernelGGL(k_accumulate_tail, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, n);
-  }
   return hipGetLastError();
 }
 

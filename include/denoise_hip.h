@@ -251,7 +251,9 @@ dn_status dn_structure_loss(const float* pred, const float* pred2, const float* 
 /* ---- optimiser: torch.optim.Adam as used at train.py:332, :368 --------------------- */
 /* One fused Adam step over n floats (torch _single_tensor_adam math, amsgrad=False,
    weight_decay=0).  step is the 1-based step count after increment.  grad_scale multiplies
-   the gradient first (1/world_size after an all-reduce sum). */
+   the gradient first (1/world_size after an all-reduce sum).  lr and the betas are read as the
+   shortest decimal that rounds to the fp32 argument (0.999f means 0.999), so that 1 - beta,
+   beta^step and lr / (1 - beta1^step) are the doubles torch forms from its Python floats. */
 dn_status dn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                        float lr, float beta1, float beta2, float eps, int64_t step,
                        float grad_scale, void* stream);
