@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_size_t, c_uint8, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint8, c_uint64, c_void_p
 
 import torch
 
@@ -171,6 +171,14 @@ SIGNATURES = {
                                     c_void_p, c_size_t, c_void_p]),
     "dn_finetune_loss": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_float, _F, _F, c_void_p,
                                  c_void_p]),
+    "dn_iqsl_partials_size": (c_size_t, []),
+    "dn_finetune_iqsl_loss": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_float, c_float,
+                                      c_double, c_double, c_double, c_double, c_double, _F, _F,
+                                      c_void_p, c_void_p]),
+    "dn_iqsl_loss": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
+                             c_double, c_double, _F, _F, c_void_p, c_void_p]),
+    "dn_iq_iou_u8": (c_int, [_U8, _U8, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                             c_void_p]),
 }
 
 _lib = None

@@ -7,6 +7,9 @@
 * `load_checkpoint` reads a reference checkpoint with or without that prefix, stripping it the
   way `finetune.py:207-218` does, through `torch.load(weights_only=True)` (no unpickling of code).
 
+* `save_adapter_checkpoint` / `load_adapter_checkpoint` pair a base checkpoint with the
+  adapter-only files `epoch_adapter_only_{epoch:03d}.pth` of `finetune_iqsl.py:114-132`.
+
 The keys and shapes are those of `arch_unet.UNet` (`arch_unet.py:115-192`); our `UNet` keeps
 its parameters as views of one flat buffer, so loading is one copy per tensor.
 """
@@ -42,6 +45,23 @@ def load_checkpoint(net: torch.nn.Module, path: str, strict: bool = True):
 def checkpoint_name(epoch: int, name: str) -> str:
     """train.py:49 file name"""
     return "epoch_{}_{:03d}.pth".format(name, epoch)
+
+
+def adapter_checkpoint_name(epoch: int) -> str:
+    """finetune_iqsl.py:122 file name of an adapter-only checkpoint"""
+    return "epoch_adapter_only_{:03d}.pth".format(epoch)
+
+
+def save_adapter_checkpoint(model: torch.nn.Module, path: str) -> str:
+    """torch.save(model.adapter.state_dict()) (finetune_iqsl.py:114-132): the adapter's four
+    tensors alone, keys `net.0.weight` .. `net.2.bias`, on the CPU."""
+    return save_checkpoint(model.adapter, path)
+
+
+def load_adapter_checkpoint(model: torch.nn.Module, path: str):
+    """evaluation_adapter_iqsl.py:90-108: an adapter-only state into `model.adapter`, non-strict;
+    returns torch's (missing, unexpected)"""
+    return model.adapter.load_state_dict(read_state_dict(path), strict=False)
 
 
 def save_checkpoint(net: torch.nn.Module, path: str, data_parallel: bool = False) -> str:

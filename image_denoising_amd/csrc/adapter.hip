@@ -342,6 +342,205 @@ __global__ __launch_bounds__(256) void k_ft_finalize(const double* __restrict__ 
   loss3[2] = l1 + lam * lg;
 }
 
+// ---- IQSL finetune loss (finetune_iqsl.py:291-383, :476-491) ---------------------------------
+// loss = L1 + lambda_grad * gradient_loss + lambda_iqsl * iqsl, iqsl = L_dice + ce_factor * ce of
+// a 3-class (dark / mid / bright) soft segmentation of the prediction against the thresholded
+// target.  iqsl's gradient at a pixel depends on sums over the whole batch, so:
+//   k_iqsl_sums      one pass: the L1 / gradient-L1 sums and their gradient exactly as k_ft_loss
+//                    forms them (same bits), plus the eleven IQSL sums, per block in fp64
+//   k_iqsl_finalize  fixed-order sum of the block partials -> loss4 and the coefficients
+//                    D_k, 2 I_k + eps, 3 V + eps, left behind the partials
+//   k_iqsl_grad      second pass: dpred += lambda_iqsl * d iqsl / d pred
+// Thresholds and centres arrive rounded to fp32 (torch compares an fp32 tensor with a Python
+// float rounded to fp32, and builds the centres as an fp32 tensor); compares and z - c_k are
+// fp32, everything after that fp64.
+constexpr int kIqTerms = 16;  // slots per block: 0-2 L1 | 3-5 I_k | 6-8 P_k | 9-11 T_k | 12 S | 13 V
+constexpr int kIqUsed = 14;
+constexpr int kIqCoefs = 8;   // D_0..2, (2 I_k + eps)_0..2, 3 V + eps, iqsl
+constexpr double kIqEps = 1e-6;
+
+size_t iqsl_partials_bytes() { return sizeof(double) * (kFtBlocks * kIqTerms + kIqCoefs); }
+
+// the pixel's valid flag and class (-1: a NaN target belongs to none) from the fp32 target
+__device__ __forceinline__ bool iq_valid(const IqslScalars& a, float y) {
+  if (!a.use_margin) return true;
+  return y <= a.t1_lo || (y >= a.t1_hi && y <= a.t2_lo) || y >= a.t2_hi;
+}
+
+__device__ __forceinline__ int iq_class(const IqslScalars& a, float y) {
+  if (y <= a.t1) return 0;
+  if (y >= a.t2) return 2;
+  return (y > a.t1 && y < a.t2) ? 1 : -1;
+}
+
+// p = softmax_k(-|z - c_k| / tau)
+__device__ __forceinline__ void iq_prob(const IqslScalars& a, float z, double p[3]) {
+  double l[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) l[k] = -(double)fabsf(z - a.c[k]) / a.tau;
+  const double m = fmax(fmax(l[0], l[1]), l[2]);
+  double sum = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p[k] = exp(l[k] - m);
+    sum += p[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] /= sum;
+}
+
+template <bool L1>
+__global__ __launch_bounds__(256) void k_iqsl_sums(const float* __restrict__ p,
+                                                   const float* __restrict__ t, int N, int C, int H,
+                                                   int W, float g0, float gx, float gy,
+                                                   IqslScalars a, float* __restrict__ dp,
+                                                   double* __restrict__ partials) {
+  const long total = (long)N * C * H * W;
+  double v[kIqUsed];
+#pragma unroll
+  for (int k = 0; k < kIqUsed; ++k) v[k] = 0.0;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const float pe = p[e], te = t[e];
+    if (L1) {  // k_ft_loss's body, term for term
+      const int x = (int)(e % W);
+      const int y = (int)((e / W) % H);
+      const float d0 = pe - te;
+      v[0] += fabs((double)d0);
+      float g = g0 * sgn1(d0);
+      if (x + 1 < W) {
+        const float b = (p[e + 1] - pe) - (t[e + 1] - te);
+        v[1] += fabs((double)b);
+        g -= gx * sgn1(b);
+      }
+      if (x > 0) g += gx * sgn1((pe - p[e - 1]) - (te - t[e - 1]));
+      if (y + 1 < H) {
+        const float b = (p[e + W] - pe) - (t[e + W] - te);
+        v[2] += fabs((double)b);
+        g -= gy * sgn1(b);
+      }
+      if (y > 0) g += gy * sgn1((pe - p[e - W]) - (te - t[e - W]));
+      dp[e] = g;
+    }
+    if (!iq_valid(a, te)) continue;
+    double q[3];
+    iq_prob(a, pe, q);
+    const int cls = iq_class(a, te);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      v[6 + k] += q[k];
+      if (k == cls) {
+        v[3 + k] += q[k];
+        v[9 + k] += 1.0;
+        v[12] += log(q[k] + kIqEps);
+      }
+    }
+    v[13] += 1.0;
+  }
+  __shared__ double red[4][kIqUsed];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kIqUsed; ++k) v[k] = wsum64(v[k]);
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < kIqUsed; ++k) red[wv][k] = v[k];
+  __syncthreads();
+  if (threadIdx.x < kIqUsed) {
+    const int k = threadIdx.x;
+    partials[blockIdx.x * kIqTerms + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
+// loss: [loss_l1, loss_grad, loss_iqsl, total] when L1, [loss_iqsl] otherwise
+template <bool L1>
+__global__ __launch_bounds__(256) void k_iqsl_finalize(double* __restrict__ partials, int nblk,
+                                                       double M, double Mx, double My, float lam,
+                                                       float lam_iq, double ce_factor,
+                                                       float* __restrict__ loss) {
+  __shared__ double sh[kIqUsed][256];
+  const int t = threadIdx.x;
+  double v[kIqUsed];
+#pragma unroll
+  for (int k = 0; k < kIqUsed; ++k) v[k] = 0.0;
+  for (int b = t; b < nblk; b += 256)
+#pragma unroll
+    for (int k = 0; k < kIqUsed; ++k) v[k] += partials[b * kIqTerms + k];
+#pragma unroll
+  for (int k = 0; k < kIqUsed; ++k) sh[k][t] = v[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w)
+#pragma unroll
+      for (int k = 0; k < kIqUsed; ++k) sh[k][t] += sh[k][t + w];
+    __syncthreads();
+  }
+  if (t != 0) return;
+  double* coef = partials + (long)nblk * kIqTerms;
+  double dice = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    const double D = sh[6 + k][0] + sh[9 + k][0] + kIqEps, Nk = 2.0 * sh[3 + k][0] + kIqEps;
+    coef[k] = D;
+    coef[3 + k] = Nk;
+    dice += Nk / D;
+  }
+  const double VV = 3.0 * sh[13][0] + kIqEps;
+  const double iq = (1.0 - dice / 3.0) + ce_factor * (-sh[12][0] / VV);
+  coef[6] = VV;
+  coef[7] = iq;
+  if (L1) {
+    const float l1 = (float)(sh[0][0] / M);
+    const float lg = (float)(sh[1][0] / Mx) + (float)(sh[2][0] / My);
+    loss[0] = l1;
+    loss[1] = lg;
+    loss[2] = (float)iq;
+    loss[3] = (l1 + lam * lg) + lam_iq * (float)iq;
+  } else {
+    loss[0] = (float)iq;
+  }
+}
+
+// d iqsl / dz = v sum_k a_k p_k (s_k - r), a_k = d iqsl / d q_k, s_k = -sgn(z - c_k) / tau,
+// r = sum_j p_j s_j.  ACC: dp += lam_iq * that (an invalid pixel is not touched); else dp = that.
+template <bool ACC>
+__global__ __launch_bounds__(256) void k_iqsl_grad(const float* __restrict__ p,
+                                                   const float* __restrict__ t, long total,
+                                                   IqslScalars a, float lam_iq, double ce_factor,
+                                                   const double* __restrict__ coef,
+                                                   float* __restrict__ dp) {
+  double A[3], B[3];  // a_k = A_k - [k == class] (B_k + cv / (q_k + eps))
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double D = coef[k];
+    A[k] = coef[3 + k] / (3.0 * D * D);
+    B[k] = 2.0 / (3.0 * D);
+  }
+  const double cv = ce_factor / coef[6];
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const float pe = p[e], te = t[e];
+    if (!iq_valid(a, te)) {
+      if (!ACC) dp[e] = 0.f;
+      continue;
+    }
+    double q[3], s[3];
+    iq_prob(a, pe, q);
+    const int cls = iq_class(a, te);
+    double r = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s[k] = -(double)sgn1(pe - a.c[k]) / a.tau;
+      r += q[k] * s[k];
+    }
+    double g = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double ak = A[k];
+      if (k == cls) ak -= B[k] + cv / (q[k] + kIqEps);
+      g += ak * q[k] * (s[k] - r);
+    }
+    if (ACC) dp[e] = dp[e] + (float)((double)lam_iq * g);
+    else dp[e] = (float)g;
+  }
+}
+
 // ---- launchers ------------------------------------------------------------------------------
 long adapter_param_count(int C) {
   if (C == 1) return AdCfg<1>::NP;
@@ -389,6 +588,43 @@ hipError_t launch_ft_loss(const float* pred, const float* tgt, int N, int C, int
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_ft_finalize, dim3(1), dim3(256), 0, s, part, kFtBlocks, M, Mx, My, lam, loss3);
+  return hipGetLastError();
+}
+
+// with_l1: the finetune_iqsl.py total (loss = 4 floats, dpred its gradient; lam_iq == 0 leaves
+// dpred as launch_ft_loss writes it).  Otherwise iqsl alone (loss = 1 float, dpred = d iqsl).
+hipError_t launch_iqsl_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
+                            float lam, float lam_iq, const IqslScalars& a, double ce_factor,
+                            bool with_l1, float* dpred, float* loss, void* partials,
+                            hipStream_t s) {
+  const double M = (double)N * C * H * W;
+  const double Mx = (double)N * C * H * (W - 1), My = (double)N * C * (H - 1) * W;
+  const float g0 = 1.0f / (float)M, gx = lam / (float)Mx, gy = lam / (float)My;  // launch_ft_loss's
+  double* part = static_cast<double*>(partials);
+  const double* coef = part + (long)kFtBlocks * kIqTerms;
+  const long total = (long)N * C * H * W;
+  const dim3 grid(kFtBlocks), blk(256);
+  hipError_t e;
+  if (with_l1) {
+    hipLaunchKernelGGL(k_iqsl_sums<true>, grid, blk, 0, s, pred, tgt, N, C, H, W, g0, gx, gy, a,
+                       dpred, part);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_iqsl_finalize<true>, dim3(1), blk, 0, s, part, kFtBlocks, M, Mx, My, lam,
+                       lam_iq, ce_factor, loss);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (lam_iq == 0.f) return hipSuccess;
+    hipLaunchKernelGGL(k_iqsl_grad<true>, grid, blk, 0, s, pred, tgt, total, a, lam_iq, ce_factor,
+                       coef, dpred);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_iqsl_sums<false>, grid, blk, 0, s, pred, tgt, N, C, H, W, g0, gx, gy, a,
+                     dpred, part);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_iqsl_finalize<false>, dim3(1), blk, 0, s, part, kFtBlocks, M, Mx, My, lam,
+                     lam_iq, ce_factor, loss);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_iqsl_grad<false>, grid, blk, 0, s, pred, tgt, total, a, 1.f, ce_factor, coef,
+                     dpred);
   return hipGetLastError();
 }
 

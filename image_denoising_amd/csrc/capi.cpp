@@ -983,6 +983,68 @@ dn_status dn_finetune_loss(const float* pred, const float* target, int N, int C,
                     "dn_finetune_loss");
 }
 
+// ---- IQSL finetune loss (finetune_iqsl.py:291-383) ---------------------------------------------
+size_t dn_iqsl_partials_size(void) { return iqsl_partials_bytes(); }
+
+// validates IQSL's scalars and forms what the kernels compare with: each value in double, rounded
+// once to fp32 (torch rounds a Python float to the tensor's dtype before it compares)
+static dn_status iqsl_scalars(int N, int C, int H, int W, double t1, double t2, double tau,
+                              double margin, double ce_factor, IqslScalars& a) {
+  if (C != 1) return fail(DN_ERR_ARG, "IQSL assumes single-channel input: C must be 1");
+  if (N < 1 || H < 2 || W < 2) return fail(DN_ERR_ARG, "gradient_loss needs H, W >= 2");
+  if (!std::isfinite(t1) || !std::isfinite(t2)) return fail(DN_ERR_ARG, "IQSL thresholds must be finite");
+  if (!std::isfinite(tau) || !std::isfinite(margin) || !std::isfinite(ce_factor))
+    return fail(DN_ERR_ARG, "IQSL tau, margin and ce_factor must be finite");
+  if (!(t1 < t2) || !((float)t1 < (float)t2))
+    return fail(DN_ERR_ARG, "IQSL needs t1 < t2 (as fp32 values too)");
+  a.t1 = (float)t1;
+  a.t2 = (float)t2;
+  a.t1_lo = (float)(t1 - margin);
+  a.t1_hi = (float)(t1 + margin);
+  a.t2_lo = (float)(t2 - margin);
+  a.t2_hi = (float)(t2 + margin);
+  a.c[0] = (float)(t1 / 2.0);
+  a.c[1] = (float)((t1 + t2) / 2.0);
+  a.c[2] = (float)((t2 + 1.0) / 2.0);
+  a.use_margin = margin > 0.0;
+  a.tau = tau > 1e-6 ? tau : 1e-6;
+  return DN_OK;
+}
+
+dn_status dn_finetune_iqsl_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                                float lambda_grad, float lambda_iqsl, double t1, double t2,
+                                double tau, double margin, double ce_factor, float* dpred,
+                                float* loss4, void* partial_ws, void* stream) {
+  if (!pred || !target || !dpred || !loss4 || !partial_ws) return fail(DN_ERR_ARG, "null argument");
+  IqslScalars a;
+  if (dn_status st = iqsl_scalars(N, C, H, W, t1, t2, tau, margin, ce_factor, a)) return st;
+  const OpTimer timer((hipStream_t)stream, "loss_iqsl", 0, 0, 0, H, W, N);
+  return hip_status(launch_iqsl_loss(pred, target, N, C, H, W, lambda_grad, lambda_iqsl, a,
+                                     ce_factor, true, dpred, loss4, partial_ws, (hipStream_t)stream),
+                    "dn_finetune_iqsl_loss");
+}
+
+dn_status dn_iqsl_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                       double t1, double t2, double tau, double margin, double ce_factor,
+                       float* dpred, float* loss1, void* partial_ws, void* stream) {
+  if (!pred || !target || !dpred || !loss1 || !partial_ws) return fail(DN_ERR_ARG, "null argument");
+  IqslScalars a;
+  if (dn_status st = iqsl_scalars(N, C, H, W, t1, t2, tau, margin, ce_factor, a)) return st;
+  return hip_status(launch_iqsl_loss(pred, target, N, C, H, W, 0.f, 1.f, a, ce_factor, false, dpred,
+                                     loss1, partial_ws, (hipStream_t)stream),
+                    "dn_iqsl_loss");
+}
+
+dn_status dn_iq_iou_u8(const uint8_t* pred, const uint8_t* clean, int C, int H, int W, double t1,
+                       double t2, void* part, int64_t* counts6, void* stream) {
+  if (!pred || !clean || !part || !counts6) return fail(DN_ERR_ARG, "null argument");
+  if (C < 1 || C > 65536 || H < 1 || W < 1) return fail(DN_ERR_ARG, "need 1 <= C <= 65536 and H, W >= 1");
+  if (std::isnan(t1) || std::isnan(t2) || t1 > t2) return fail(DN_ERR_ARG, "need t1 <= t2, neither NaN");
+  return hip_status(launch_iq_iou(pred, clean, C, (long)H * W, t1, t2, part, counts6,
+                                  (hipStream_t)stream),
+                    "dn_iq_iou_u8");
+}
+
 // ---- ImprovedUNet (arch_unet.py:421-531) ------------------------------------------------------
 dn_status dn_iunet_param_count(const dn_unet_cfg* cfg, size_t* count) {
   DN_GUARD_BEGIN

@@ -335,6 +335,8 @@ hipError_t launch_l1_batched(const float* a, const float* b, long P, long n, dou
                              hipStream_t s);
 hipError_t launch_l1(const float* a, const float* b, long n, double* part, double* out,
                      hipStream_t s);
+hipError_t launch_iq_iou(const uint8_t* pred, const uint8_t* clean, int C, long HW, double t1,
+                         double t2, void* part, int64_t* counts6, hipStream_t s);
 hipError_t launch_head_bwd(const HeadBwdArgs& h, hipStream_t s);
 int wgrad_thin_splits(long npx);
 hipError_t launch_wgrad_c3_thin(const float* g, int cout, const float* x, int N, int C, int H,
@@ -482,5 +484,19 @@ hipError_t launch_adapter_bwd(const float* prm, const float* noisy, const float*
                               float* slab, hipStream_t s);
 hipError_t launch_ft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
                           float lam, float* dpred, float* loss3, void* partials, hipStream_t s);
+// IQSL's scalars as the kernels use them: each comparison value and centre formed in double on
+// the host and rounded once to fp32; tau already clamped to >= 1e-6
+struct IqslScalars {
+  float t1, t2;                        // dark: y <= t1, bright: y >= t2
+  float t1_lo, t1_hi, t2_lo, t2_hi;    // t1 -+ margin, t2 -+ margin
+  float c[3];                          // t1 / 2, (t1 + t2) / 2, (t2 + 1) / 2
+  int use_margin;                      // margin > 0
+  double tau;
+};
+size_t iqsl_partials_bytes();
+hipError_t launch_iqsl_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
+                            float lam, float lam_iq, const IqslScalars& a, double ce_factor,
+                            bool with_l1, float* dpred, float* loss, void* partials,
+                            hipStream_t s);
 
 }  // namespace dn

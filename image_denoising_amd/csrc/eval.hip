@@ -13,6 +13,8 @@
 //   k_ssim_part      11x11 Gaussian (sigma 1.5) window statistics in fp64 over the valid
 //                    region [5, H-5) x [5, W-5), SSIM map summed per block utils_eval.py:19-33
 //   k_l1_part        sum |a - b| in fp64                           evaluation.py:74 (nn.L1Loss)
+//   k_iq_iou_part    3-class intensity labels of two images, exact intersection / union counts
+//                                                                 evaluation_adapter_iqsl.py:122-159
 //   k_eval_finalize  fixed-order sum of the block partials -> metric (deterministic)
 #include <cstdint>
 
@@ -223,6 +225,58 @@ __global__ __launch_bounds__(256) void k_eval_finalize(const double* __restrict_
   out[0] = kind == 0 ? 10.0 * log10(255.0 * 255.0 / mean) : mean;
 }
 
+// IQ-IoU (evaluation_adapter_iqsl.py:122-159): gray = mean over channels / 255 formed in fp32
+// with true divisions as numpy forms it, compared in fp64 with the quantile thresholds; label 2
+// (gray >= t2) is assigned last there, so it wins when t1 == t2.  Per block: intersection and
+// union counts of the three classes, exact integers.
+constexpr int IQ_BLOCKS = 128;  // 6 slots per block fit dn_eval_partials_size()
+static_assert(IQ_BLOCKS * 6 <= EVAL_PARTS, "IQ-IoU partials exceed the evaluation workspace");
+
+__device__ __forceinline__ int iq_label(const uint8_t* __restrict__ img, int C, long HW, long i,
+                                        double t1, double t2) {
+#pragma clang fp contract(off)
+  int sum = 0;
+  for (int c = 0; c < C; ++c) sum += img[(long)c * HW + i];
+  float g = (float)sum;
+  if (C > 1) g = g / (float)C;
+  const double gray = (double)(g / 255.0f);
+  return gray >= t2 ? 2 : (gray > t1 ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void k_iq_iou_part(const uint8_t* __restrict__ pred,
+                                                     const uint8_t* __restrict__ clean, int C,
+                                                     long HW, double t1, double t2,
+                                                     unsigned long long* __restrict__ part) {
+  __shared__ unsigned int sh[6][256];
+  unsigned int cnt[6] = {0, 0, 0, 0, 0, 0};  // inter_0..2, union_0..2 (a thread sees < 2^32 pixels)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+    const int lp = iq_label(pred, C, HW, i, t1, t2), lc = iq_label(clean, C, HW, i, t1, t2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      cnt[k] += (lp == k && lc == k) ? 1u : 0u;
+      cnt[3 + k] += (lp == k || lc == k) ? 1u : 0u;
+    }
+  }
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) sh[k][t] = cnt[k];
+  __syncthreads();
+  if (t < 6) {
+    unsigned long long s = 0;
+    for (int j = 0; j < 256; ++j) s += sh[t][j];
+    part[blockIdx.x * 6 + t] = s;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_iq_iou_finalize(const unsigned long long* __restrict__ part,
+                                                        int nblk, int64_t* __restrict__ counts6) {
+  const int t = threadIdx.x;
+  if (t >= 6) return;
+  unsigned long long s = 0;
+  for (int b = 0; b < nblk; ++b) s += part[b * 6 + t];
+  counts6[t] = (int64_t)s;
+}
+
 static unsigned blocks_for(long n) {
   long b = (n + 255) / 256;
   if (b > EVAL_BLOCKS) b = EVAL_BLOCKS;
@@ -277,6 +331,16 @@ hipError_t launch_ssim(const uint8_t* a, const uint8_t* b, int C, int H, int W, 
 hipError_t launch_l1_batched(const float* a, const float* b, long P, long n, double* out,
                              hipStream_t s) {
   hipLaunchKernelGGL(k_l1_batched, dim3((unsigned)P), dim3(256), 0, s, a, b, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_iq_iou(const uint8_t* pred, const uint8_t* clean, int C, long HW, double t1,
+                         double t2, void* part, int64_t* counts6, hipStream_t s) {
+  unsigned nb = blocks_for(HW);
+  if (nb > IQ_BLOCKS) nb = IQ_BLOCKS;
+  unsigned long long* p = static_cast<unsigned long long*>(part);
+  hipLaunchKernelGGL(k_iq_iou_part, dim3(nb), dim3(256), 0, s, pred, clean, C, HW, t1, t2, p);
+  hipLaunchKernelGGL(k_iq_iou_finalize, dim3(1), dim3(64), 0, s, p, (int)nb, counts6);
   return hipGetLastError();
 }
 

@@ -96,6 +96,51 @@ def calculate_ssim(target, ref) -> float:
     return float(ssim_device(a, b, hwc=a.dim() == 3).item())
 
 
+def iq_iou_counts_device(pred8: torch.Tensor, clean8: torch.Tensor, t1: float, t2: float):
+    """device int64 [6]: intersection of the classes dark / mid / bright, then their unions, of
+    two uint8 [C,H,W] (or [H,W]) device images labelled by gray <= t1 / between / gray >= t2"""
+    pred8, clean8 = _chw(pred8), _chw(clean8)
+    if pred8.shape != clean8.shape:
+        raise ValueError("Input images must have the same dimensions.")
+    C, H, W = pred8.shape
+    counts = torch.empty(6, dtype=torch.int64, device=pred8.device)
+    _lib.call("dn_iq_iou_u8", _lib.ptr(pred8), _lib.ptr(clean8), C, H, W, float(t1), float(t2),
+              _lib.ptr(_parts(pred8.device)), _lib.ptr(counts), _lib.stream_of(pred8))
+    return counts
+
+
+def _u8_image(img) -> np.ndarray:
+    """[H,W] or [H,W,C] host image with values 0..255 (uint8, or the float32 the reference reads
+    its clean images as) -> uint8, unchanged in value"""
+    a = img.cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    if a.dtype != np.uint8:
+        b = a.astype(np.uint8)
+        if not np.array_equal(b.astype(a.dtype), a):
+            raise ValueError("IQ-IoU images must hold whole numbers in 0..255")
+        a = b
+    if a.ndim not in (2, 3):
+        raise ValueError("Wrong input image dimensions.")
+    return a
+
+
+def compute_iq_iou(pred255, clean255, low_q: float, high_q: float):
+    """evaluation_adapter_iqsl.py:137-159: [IoU dark, IoU mid, IoU bright] of the 3-class
+    intensity quantisation of two [H,W] / [H,W,C] images (channel-last, as PIL gives them) at the
+    clean image's low_q / high_q quantiles; nan for a class neither image has.  The quantiles are
+    numpy's on the host, as there; labels and counts run on the device (dn_iq_iou_u8), one host
+    read of six integers."""
+    dev = _device()
+    pred, clean = _u8_image(pred255), _u8_image(clean255)
+    gray = clean.astype(np.float32)
+    if gray.ndim == 3:
+        gray = gray.mean(axis=2)
+    t1, t2 = np.quantile(gray / 255.0, [low_q, high_q])
+    chw = lambda a: a if a.ndim == 2 else np.ascontiguousarray(a.transpose(2, 0, 1))  # noqa: E731
+    n = iq_iou_counts_device(_u8(chw(pred), dev), _u8(chw(clean), dev), float(t1), float(t2))
+    n = n.cpu().numpy()
+    return [float(n[k]) / float(n[3 + k]) if n[3 + k] else float("nan") for k in range(3)]
+
+
 def weight_mask(patch: int = PATCH) -> np.ndarray:
     """evaluation_704.py:62-68 (computed in float64, stored as float32)"""
     yy, xx = np.meshgrid(np.linspace(0, 1, patch), np.linspace(0, 1, patch), indexing="ij")

@@ -1,12 +1,19 @@
-"""evaluation_adapter.py on the HIP path: inference of a DenoiserWithAdapter checkpoint
-(frozen base + OutputAdapter, adapter.py:29-67) over <data_dir>/noise/*, saving
+"""evaluation_adapter.py / evaluation_adapter_iqsl.py on the HIP path: inference of a
+DenoiserWithAdapter (frozen base + OutputAdapter, adapter.py:29-67) over <data_dir>/noise/*, saving
 <name>_denoised.png and, when <data_dir>/clean/ exists, printing each image's PSNR
-(evaluation_adapter.py:63-166).
+(evaluation_adapter.py:63-166) and, with --compute_iq_iou, its 3-class intensity-quantised IoU
+and the nanmean averages (evaluation_adapter_iqsl.py:245-273).
 
     python -m image_denoising_amd.evaluation_adapter --data_dir D --ckpt X.pth [--arch UNet]
+    python -m image_denoising_amd.evaluation_adapter --data_dir D --base_ckpt B.pth \
+        --adapter_ckpt epoch_adapter_only_020.pth [--compute_iq_iou]
+
+--ckpt is one file with `base.*` and `adapter.*` keys (finetune.py's checkpoint); --base_ckpt +
+--adapter_ckpt pair the base's own checkpoint with the adapter-only file finetune_iqsl.py writes.
 
 The base runs on the HIP executors (UNet or ImprovedUNet), the adapter on dn_adapter_forward;
-quantisation (clip(x*255 + 0.5) -> uint8) and PSNR on device (dn_quantize_u8, dn_psnr_u8).
+quantisation (clip(x*255 + 0.5) -> uint8), PSNR and the IoU counts on device (dn_quantize_u8,
+dn_psnr_u8, dn_iq_iou_u8).
 """
 from __future__ import annotations
 
@@ -18,14 +25,17 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluation import _device, psnr_device
+from .evaluation import _device, compute_iq_iou, psnr_device
 
 
 def parse_args(argv=None):
-    """evaluation_adapter.py:17-43 (parse_known_args: unknown options are ignored there too)"""
+    """evaluation_adapter.py:17-43, evaluation_adapter_iqsl.py:17-62 (parse_known_args: unknown
+    options are ignored there too)"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_dir", type=str, required=True)
-    ap.add_argument("--ckpt", type=str, required=True)
+    ap.add_argument("--ckpt", type=str, default=None)
+    ap.add_argument("--base_ckpt", type=str, default=None)
+    ap.add_argument("--adapter_ckpt", type=str, default=None)
     ap.add_argument("--arch", type=str, default="UNetImproved", choices=["UNet", "RESNET", "UNetImproved"])
     ap.add_argument("--save_dir", type=str, default="./results_infer_adapter")
     ap.add_argument("--gpu_devices", default="0", type=str)
@@ -33,7 +43,15 @@ def parse_args(argv=None):
     ap.add_argument("--n_feature", type=int, default=48)
     ap.add_argument("--n_channel", type=int, default=1)
     ap.add_argument("--adapter_hidden", type=int, default=16)
+    ap.add_argument("--compute_iq_iou", action="store_true")
+    ap.add_argument("--iq_low_q", type=float, default=0.25)
+    ap.add_argument("--iq_high_q", type=float, default=0.75)
     args, _ = ap.parse_known_args(argv)
+    paired = args.base_ckpt is not None or args.adapter_ckpt is not None
+    if paired and (args.ckpt is not None or args.base_ckpt is None or args.adapter_ckpt is None):
+        ap.error("give either --ckpt, or --base_ckpt together with --adapter_ckpt")
+    if not paired and args.ckpt is None:
+        ap.error("one of --ckpt or --base_ckpt/--adapter_ckpt is required")
     return args
 
 
@@ -57,6 +75,25 @@ def load_adapter_weights(model, ckpt_path: str):
     if unexpected:
         print(f"[Warning] Unexpected keys when loading adapter model: {unexpected}")
     print(f"Loaded adapter+base weights from {ckpt_path}")
+
+
+def load_base_and_adapter(model, base_ckpt: str, adapter_ckpt: str):
+    """evaluation_adapter_iqsl.py:76-108: the base's checkpoint into model.base (non-strict,
+    'module.' prefix stripped), then the adapter-only state into model.adapter (non-strict)"""
+    from .checkpoint import load_adapter_checkpoint, load_checkpoint
+
+    missing, unexpected = load_checkpoint(model.base, base_ckpt, strict=False)
+    if missing:
+        print(f"[Warning] Missing keys when loading base model: {missing}")
+    if unexpected:
+        print(f"[Warning] Unexpected keys when loading base model: {unexpected}")
+    print(f"Loaded base weights from {base_ckpt}")
+    missing, unexpected = load_adapter_checkpoint(model, adapter_ckpt)
+    if missing:
+        print(f"[Warning] Missing keys when loading adapter: {missing}")
+    if unexpected:
+        print(f"[Warning] Unexpected keys when loading adapter: {unexpected}")
+    print(f"Loaded adapter-only weights from {adapter_ckpt}")
 
 
 @torch.no_grad()
@@ -90,8 +127,11 @@ def main(argv=None):
     print(f"Found {len(noise_paths)} noisy images for inference.")
     model = build_model(opt.arch, opt.n_channel, opt.n_feature, opt.adapter_hidden).to(_device())
     model.eval()
-    load_adapter_weights(model, opt.ckpt)
-    psnrs = []
+    if opt.ckpt is not None:
+        load_adapter_weights(model, opt.ckpt)
+    else:
+        load_base_and_adapter(model, opt.base_ckpt, opt.adapter_ckpt)
+    psnrs, ious = [], []
     for idx, n_path in enumerate(noise_paths):
         name = os.path.basename(n_path)
         base_name = os.path.splitext(name)[0]
@@ -109,11 +149,24 @@ def main(argv=None):
             # evaluation_adapter.py:75-83: mse == 0 -> 99.0
             ps = 99.0 if torch.equal(p8, c8) else float(psnr_device(p8, c8).cpu())
             psnrs.append(ps)
-            print(f"[{idx + 1:03d}/{len(noise_paths):03d}] {name} → PSNR={ps:.2f} dB, saved to {save_path}")
+            msg = f"[{idx + 1:03d}/{len(noise_paths):03d}] {name} → PSNR={ps:.2f} dB, saved to {save_path}"
+            if opt.compute_iq_iou:
+                pred_hw = out[0] if out.shape[0] == 1 else np.transpose(out, (1, 2, 0))
+                iou = compute_iq_iou(pred_hw, clean, opt.iq_low_q, opt.iq_high_q)
+                ious.append(iou)
+                msg += f", IoU(d/m/b)=({iou[0]:.3f},{iou[1]:.3f},{iou[2]:.3f})"
+            print(msg)
         else:
             print(f"[{idx + 1:03d}/{len(noise_paths):03d}] {name} → saved to {save_path}")
+    res = dict(psnr=psnrs)
+    if opt.compute_iq_iou and ious:
+        res["iq_iou"] = ious
+        with np.errstate(all="ignore"):
+            res["avg_iq_iou"] = [float(v) for v in np.nanmean(np.array(ious, np.float64), axis=0)]
+        d, m, b = res["avg_iq_iou"]
+        print(f"Average IQ-3class IoU - dark: {d:.4f}, mid: {m:.4f}, bright: {b:.4f}")
     print("Inference with adapter model finished.")
-    return dict(psnr=psnrs)
+    return res
 
 
 if __name__ == "__main__":

@@ -4,6 +4,7 @@ OutputAdapter, trained with L1 + lambda_grad * gradient_loss on random patches.
     base_out = base(noisy)           [no grad]   dn_unet_forward        (adapter.py:59-61)
     pred     = adapter(noisy, base_out)          dn_adapter_forward     (adapter.py:22-26)
     loss3, dpred = L1 + lambda*grad-L1           dn_finetune_loss       (finetune.py:153-162, :283-285)
+      [+ lambda_iqsl * iqsl -> loss4]            dn_finetune_iqsl_loss  (finetune_iqsl.py:291-383)
     dA       = adapter backward(dpred)           dn_adapter_backward
     [data parallel: one RCCL all-reduce(sum) of the 449-float gradient]
     Adam(A, dA / world)                          dn_adam_step           (finetune.py:246-249, :288)
@@ -75,6 +76,93 @@ class FinetuneLoss(nn.Module):
         return _FinetuneLossFn.apply(pred, target, self.lambda_grad, 2)
 
 
+_iqsl_partials = {}
+
+
+def _iqsl_partials_for(device) -> torch.Tensor:
+    key = (device.type, device.index)
+    if key not in _iqsl_partials:
+        _iqsl_partials[key] = _lib.scratch(_lib.lib().dn_iqsl_partials_size(), device)
+    return _iqsl_partials[key]
+
+
+def _iqsl_inputs(pred, target):
+    """finetune_iqsl.py:309-316: [B,H,W] gets a channel axis; one shape, C == 1"""
+    if pred.dim() == 3:
+        pred = pred.unsqueeze(1)
+    if target.dim() == 3:
+        target = target.unsqueeze(1)
+    if pred.shape != target.shape or pred.dim() != 4:
+        raise ValueError("pred and target must have the same [B,1,H,W] or [B,H,W] shape")
+    if pred.shape[1] != 1:
+        raise ValueError("IQSL currently assumes single-channel grayscale input.")
+    return pred.contiguous(), target.contiguous()
+
+
+def finetune_iqsl_loss(pred: torch.Tensor, target: torch.Tensor, lambda_grad: float = 0.1,
+                       lambda_iqsl: float = 0.1, t1: float = 0.2, t2: float = 0.8,
+                       tau: float = 0.1, margin: float = 0.0, ce_factor: float = 0.5):
+    """loss_l1 + lambda_grad * gradient_loss + lambda_iqsl * iqsl_loss (finetune_iqsl.py:476-491)
+    and its gradient, no host read.  Returns (loss4 = [loss_l1, loss_grad, loss_iqsl, loss] device
+    tensor, dloss/dpred)."""
+    pred, target = _iqsl_inputs(pred, target)
+    if not float(t1) < float(t2):
+        raise ValueError(f"IQSL needs t1 < t2, got {t1}, {t2}")
+    N, C, H, W = pred.shape
+    dpred = torch.empty_like(pred)
+    loss4 = torch.empty(4, dtype=torch.float32, device=pred.device)
+    _lib.call("dn_finetune_iqsl_loss", _lib.ptr(pred), _lib.ptr(target), N, C, H, W,
+              float(lambda_grad), float(lambda_iqsl), float(t1), float(t2), float(tau),
+              float(margin), float(ce_factor), _lib.ptr(dpred), _lib.ptr(loss4),
+              _iqsl_partials_for(pred.device).data_ptr(), _lib.stream_of(pred))
+    return loss4, dpred
+
+
+class _IqslLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, t1, t2, tau, margin, ce_factor):
+        p, t = _iqsl_inputs(pred.detach(), target.detach())
+        N, C, H, W = p.shape
+        dpred = torch.empty_like(p)
+        loss = torch.empty(1, dtype=torch.float32, device=p.device)
+        _lib.call("dn_iqsl_loss", _lib.ptr(p), _lib.ptr(t), N, C, H, W, float(t1), float(t2),
+                  float(tau), float(margin), float(ce_factor), _lib.ptr(dpred), _lib.ptr(loss),
+                  _iqsl_partials_for(p.device).data_ptr(), _lib.stream_of(p))
+        ctx.save_for_backward(dpred)
+        ctx.shape = pred.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return (dpred * g).view(ctx.shape), None, None, None, None, None, None
+
+
+def iqsl_loss(pred: torch.Tensor, target: torch.Tensor, t1: float, t2: float, tau: float = 0.1,
+              margin: float = 0.0, ce_factor: float = 0.5) -> torch.Tensor:
+    """finetune_iqsl.py:291-383 (eps = 1e-6): the scalar Intensity-Quantized Structural Loss of
+    [B,1,H,W] or [B,H,W] tensors, differentiable w.r.t. pred (dn_iqsl_loss)."""
+    if not float(t1) < float(t2):
+        raise ValueError(f"IQSL needs t1 < t2, got {t1}, {t2}")
+    return _IqslLossFn.apply(pred, target, t1, t2, tau, margin, ce_factor)
+
+
+def estimate_intensity_thresholds(data_dir: str, q1: float = 0.2, q2: float = 0.8,
+                                  max_images: int = 50):
+    """finetune_iqsl.py:262-288: the q1 / q2 quantiles of every pixel / 255 of the first
+    max_images files of data_dir/clean (host code, as there)."""
+    from PIL import Image
+
+    clean_paths = sorted(glob.glob(os.path.join(data_dir, "clean", "*")))[:max_images]
+    if len(clean_paths) == 0:
+        raise RuntimeError(f"No clean images found in {os.path.join(data_dir, 'clean')}")
+    all_pixels = np.concatenate(
+        [(np.array(Image.open(p), dtype=np.float32) / 255.0).reshape(-1) for p in clean_paths], axis=0)
+    q1, q2 = float(q1), float(q2)
+    assert 0.0 < q1 < q2 < 1.0, "iqsl_q1, iqsl_q2 must satisfy 0 < q1 < q2 < 1."
+    return float(np.quantile(all_pixels, q1)), float(np.quantile(all_pixels, q2))
+
+
 class DenoisePatchDataset(torch.utils.data.Dataset):
     """finetune.py:100-150: data_dir/{clean,noise}/* paired by sorted name (first 5 images),
     len = images x patches_per_image, one random ps x ps crop per item (np.random), /255."""
@@ -137,14 +225,30 @@ def load_base_weights(model: nn.Module, ckpt_path: str):
 
 
 class FinetuneTrainer:
-    """The finetune.py:269-289 step, fused; returns loss3 = [loss_l1, loss_grad, loss]."""
+    """The finetune.py:269-289 step, fused; returns loss3 = [loss_l1, loss_grad, loss].
+
+    lambda_iqsl > 0 makes it the finetune_iqsl.py:469-494 step: `iqsl` = dict(t1, t2[, tau,
+    margin, ce_factor]) (the thresholds from `estimate_intensity_thresholds`), and the step returns
+    loss4 = [loss_l1, loss_grad, loss_iqsl, loss].  Each rank's loss is the mean over its own
+    batch, as an nn.DataParallel replica computes it."""
 
     def __init__(self, model: DenoiserWithAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
-                 distributed: bool | None = None):
+                 distributed: bool | None = None, lambda_iqsl: float = 0.0,
+                 iqsl: dict | None = None):
         if not isinstance(model, DenoiserWithAdapter):
             raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
         self.model = model
         self.lambda_grad = lambda_grad
+        self.lambda_iqsl = float(lambda_iqsl)
+        self.iqsl = None
+        if self.lambda_iqsl > 0.0:
+            if iqsl is None or "t1" not in iqsl or "t2" not in iqsl:
+                raise ValueError("lambda_iqsl > 0 needs iqsl = dict(t1=..., t2=...[, tau, margin, "
+                                 "ce_factor])")
+            unknown = set(iqsl) - {"t1", "t2", "tau", "margin", "ce_factor"}
+            if unknown:
+                raise ValueError(f"unknown IQSL settings: {sorted(unknown)}")
+            self.iqsl = dict(iqsl)
         self.distributed = dp.require_group(distributed)
         ad = model.adapter
         if self.distributed:  # identical replicas, as nn.DataParallel's per-forward broadcast
@@ -181,7 +285,11 @@ class FinetuneTrainer:
         b = self._buffers(noisy.shape, noisy.device)
         self._base_forward(noisy, b["base"])
         ad._run_forward(noisy, b["base"], b["pred"])
-        loss3, dpred = finetune_loss(b["pred"], clean, self.lambda_grad)
+        if self.iqsl is not None:
+            loss3, dpred = finetune_iqsl_loss(b["pred"], clean, self.lambda_grad, self.lambda_iqsl,
+                                              **self.iqsl)
+        else:
+            loss3, dpred = finetune_loss(b["pred"], clean, self.lambda_grad)
         ad._run_backward(noisy, b["base"], dpred, self.grad)
         scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
         self.opt.step(self.grad, grad_scale=scale)

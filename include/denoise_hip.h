@@ -384,6 +384,12 @@ dn_status dn_l1_mean(const float* a, const float* b, int64_t n, void* part, doub
    criterion(prediction_patch, noisy_input) for every tile at once, one launch; fp64 sums) */
 dn_status dn_l1_mean_batched(const float* a, const float* b, int64_t P, int64_t n, double* l1,
                              void* stream);
+/* 3-class intensity-quantised IoU counts (evaluation_adapter_iqsl.py:122-159) of two uint8 CHW
+   images: gray = fp32(fp32(sum_c x_c / C) / 255) compared as a double with t1 <= t2 (label 0:
+   gray <= t1, 1: between, 2: gray >= t2, which wins at t1 == t2); counts6 = intersection of
+   classes 0..2, then union of classes 0..2, exact.  part as above. */
+dn_status dn_iq_iou_u8(const uint8_t* pred, const uint8_t* clean, int C, int H, int W, double t1,
+                       double t2, void* part, int64_t* counts6, void* stream);
 
 /* ---- adapter finetune: adapter.py:5-67 (OutputAdapter / DenoiserWithAdapter),
    finetune.py:153-162 (gradient_loss), finetune.py:269-289 (the step) ------------------------
@@ -408,6 +414,27 @@ dn_status dn_adapter_backward(const float* params, const float* noisy, const flo
 dn_status dn_finetune_loss(const float* pred, const float* target, int N, int C, int H, int W,
                            float lambda_grad, float* dpred, float* loss3, void* partial_ws,
                            void* stream);
+/* finetune_iqsl.py:291-383, :476-491:
+     loss = L1 + lambda_grad * gradient_loss + lambda_iqsl * iqsl_loss(pred, target, t1, t2, tau,
+                                                                       margin, ce_factor)
+   IQSL: classes dark (y <= t1), mid, bright (y >= t2) of the target; p = softmax_k(-|z - c_k| /
+   max(tau, 1e-6)) of the prediction around the centres t1/2, (t1+t2)/2, (t2+1)/2; a target within
+   margin of a threshold is ignored (margin > 0); iqsl = (1 - mean_k dice_k) + ce_factor * ce,
+   eps 1e-6.  C must be 1 and t1 < t2, both finite.  The thresholds, t1 -+ margin, t2 -+ margin and
+   the centres are formed in double and rounded once to fp32, as torch does with a Python float;
+   compares and z - c_k are fp32, the rest fp64 with fixed-order sums (deterministic, no atomics,
+   no host read).  Writes loss4 = {loss_l1, loss_grad, loss_iqsl, loss} and dpred = dloss/dpred.
+   With lambda_iqsl == 0, dpred and loss4[0..1] carry dn_finetune_loss's bits.  partial_ws holds
+   dn_iqsl_partials_size() bytes. */
+size_t dn_iqsl_partials_size(void);
+dn_status dn_finetune_iqsl_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                                float lambda_grad, float lambda_iqsl, double t1, double t2,
+                                double tau, double margin, double ce_factor, float* dpred,
+                                float* loss4, void* partial_ws, void* stream);
+/* iqsl_loss alone: loss1[0] = iqsl, dpred = d iqsl / d pred (same arguments and workspace) */
+dn_status dn_iqsl_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                       double t1, double t2, double tau, double margin, double ce_factor,
+                       float* dpred, float* loss1, void* partial_ws, void* stream);
 
 /* ---- ImprovedUNet: arch_unet.py:421-531 ImprovedUNet(in_nc, out_nc, n_feature=48, depth=4,
    noise=True) — the model train.sh / evaluation.py default to (train.py:311-313) --------------
