@@ -179,6 +179,19 @@ SIGNATURES = {
                              c_double, c_double, _F, _F, c_void_p, c_void_p]),
     "dn_iq_iou_u8": (c_int, [_U8, _U8, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
                              c_void_p]),
+    "dn_memory_select_ws_size": (c_size_t, [c_int] * 7),
+    "dn_memory_select": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "dn_memory_gather": (c_int, [_F, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _F,
+                                 c_void_p]),
+    "dn_memadapter_param_count": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "dn_memadapter_ws_size": (c_size_t, [c_int] * 7),
+    "dn_memadapter_forward": (c_int, [_F, _F, _F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dn_memadapter_backward": (c_int, [_F, _F, _F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dn_hann_blend": (c_int, [_F, _F, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                              _F, c_void_p]),
 }
 
 _lib = None

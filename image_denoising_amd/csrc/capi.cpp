@@ -1279,4 +1279,113 @@ dn_status dn_conv2d_backward_weight_blocked(const float* g, int g_stride, int g_
   DN_GUARD_END
 }
 
+// ---- memory-bank adapter (finetune_memory.py, evaluation_704_iqsl_memory.py) --------------------
+static dn_status mem_geom(int n_img, int C, int H, int W, int P, int stride, MemGeom& g) {
+  if (C != 1 && C != 3) return fail(DN_ERR_ARG, "bank channels must be 1 or 3");
+  if (n_img < 1 || P < 3 || stride < 1 || H < P || W < P)
+    return fail(DN_ERR_ARG, "need n_img >= 1, patch_size >= 3, stride >= 1 and H, W >= patch_size");
+  g.n_img = n_img; g.C = C; g.H = H; g.W = W; g.P = P; g.s = stride;
+  g.ny = (H - P) / stride + 1;
+  g.nx = (W - P) / stride + 1;
+  g.N = (long)n_img * g.ny * g.nx;
+  if (g.N >= (1L << 31) || (long)n_img * C * H * W >= (1L << 40))
+    return fail(DN_ERR_ARG, "bank too large (2^31 windows)");
+  return DN_OK;
+}
+
+size_t dn_memory_select_ws_size(int B, int n_img, int C, int H, int W, int P, int stride) {
+  MemGeom g;
+  if (B < 1 || mem_geom(n_img, C, H, W, P, stride, g) != DN_OK) return 0;
+  return mem_select_ws_bytes(g, B);
+}
+
+dn_status dn_memory_select(const float* queries, const float* noise_images, int B, int n_img, int C,
+                           int H, int W, int P, int stride, int64_t* idx, void* ws,
+                           size_t ws_bytes, void* stream) {
+  if (!queries || !noise_images || !idx || !ws) return fail(DN_ERR_ARG, "null argument");
+  if (B < 1) return fail(DN_ERR_ARG, "need B >= 1");
+  MemGeom g;
+  if (dn_status st = mem_geom(n_img, C, H, W, P, stride, g)) return st;
+  if (ws_bytes < mem_select_ws_bytes(g, B))
+    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_memory_select_ws_size()");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const OpTimer timer(s, "mem_select", 2.0 * B * (double)g.N * C * P * P, 0, 0, P, P, B);
+  return hip_status(launch_mem_select(queries, noise_images, g, B, idx, ws, s), "dn_memory_select");
+}
+
+dn_status dn_memory_gather(const float* clean_images, const int64_t* idx, int B, int n_img, int C,
+                           int H, int W, int P, int stride, float* out, void* stream) {
+  if (!clean_images || !idx || !out) return fail(DN_ERR_ARG, "null argument");
+  if (B < 1) return fail(DN_ERR_ARG, "need B >= 1");
+  MemGeom g;
+  if (dn_status st = mem_geom(n_img, C, H, W, P, stride, g)) return st;
+  return hip_status(launch_mem_gather(clean_images, g, idx, B, out, (hipStream_t)stream),
+                    "dn_memory_gather");
+}
+
+static dn_status memadapter_args(int N, int C, int H, int W, int hidden, int nb) {
+  if (!memadapter_supported(C, hidden, nb))
+    return fail(DN_ERR_ARG, "need in_channels 1 or 3, hidden_channels 8 or 16, 0 <= num_fft_bins <= 8");
+  if (N < 1 || H < 1 || W < 1) return fail(DN_ERR_ARG, "empty adapter input");
+  if ((long)C * H * W < 2)
+    return fail(DN_ERR_ARG, "the unbiased std needs at least two elements per sample");
+  if (nb > 0 && W / 2 + 1 < nb) return fail(DN_ERR_ARG, "row FFT has fewer bins than num_fft_bins");
+  return DN_OK;
+}
+
+dn_status dn_memadapter_param_count(int in_channels, int hidden_channels, int num_fft_bins,
+                                    size_t* count) {
+  if (!count) return fail(DN_ERR_ARG, "null argument");
+  const long n = memadapter_param_count(in_channels, hidden_channels, num_fft_bins);
+  if (n < 0) return memadapter_args(1, in_channels, 1, 64, hidden_channels, num_fft_bins);
+  *count = (size_t)n;
+  return DN_OK;
+}
+
+size_t dn_memadapter_ws_size(int N, int C, int H, int W, int hidden_channels, int num_fft_bins,
+                             int with_backward) {
+  return memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, with_backward != 0);
+}
+
+dn_status dn_memadapter_forward(const float* params, const float* noisy, const float* base_out,
+                                const float* mem_clean, float* out, float* features, int N, int C,
+                                int H, int W, int hidden_channels, int num_fft_bins,
+                                int clamp_output, void* ws, size_t ws_bytes, void* stream) {
+  if (!params || !noisy || !base_out || !mem_clean || !out || !features || !ws)
+    return fail(DN_ERR_ARG, "null argument");
+  if (dn_status st = memadapter_args(N, C, H, W, hidden_channels, num_fft_bins)) return st;
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, false))
+    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_memadapter_ws_size()");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const OpTimer timer(s, "memadapter_fwd", 0, 0, 0, H, W, N);
+  return hip_status(launch_memadapter_fwd(params, noisy, base_out, mem_clean, out, features, N, C, H,
+                                          W, hidden_channels, num_fft_bins, clamp_output != 0, ws, s),
+                    "dn_memadapter_forward");
+}
+
+dn_status dn_memadapter_backward(const float* params, const float* noisy, const float* base_out,
+                                 const float* features, const float* dout, float* dparams, int N,
+                                 int C, int H, int W, int hidden_channels, int num_fft_bins,
+                                 int clamp_output, void* ws, size_t ws_bytes, void* stream) {
+  if (!params || !noisy || !base_out || !features || !dout || !dparams || !ws)
+    return fail(DN_ERR_ARG, "null argument");
+  if (dn_status st = memadapter_args(N, C, H, W, hidden_channels, num_fft_bins)) return st;
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, true))
+    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_memadapter_ws_size()");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const OpTimer timer(s, "memadapter_bwd", 0, 0, 0, H, W, N);
+  return hip_status(launch_memadapter_bwd(params, noisy, base_out, features, dout, dparams, N, C, H,
+                                          W, hidden_channels, num_fft_bins, clamp_output != 0, ws, s),
+                    "dn_memadapter_backward");
+}
+
+dn_status dn_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs, int ny,
+                        int nx, int C, int H, int W, int P, float* out, void* stream) {
+  if (!pred || !hann || !ys || !xs || !out) return fail(DN_ERR_ARG, "null argument");
+  if (ny < 1 || nx < 1 || C < 1 || P < 1 || H < P || W < P)
+    return fail(DN_ERR_ARG, "need ny, nx, C >= 1 and H, W >= patch_size >= 1");
+  return hip_status(launch_hann_blend(pred, hann, ys, xs, ny, nx, C, H, W, P, out,
+                                      (hipStream_t)stream), "dn_hann_blend");
+}
+
 }  // extern "C"

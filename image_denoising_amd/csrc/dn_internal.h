@@ -499,4 +499,27 @@ hipError_t launch_iqsl_loss(const float* pred, const float* tgt, int N, int C, i
                             bool with_l1, float* dpred, float* loss, void* partials,
                             hipStream_t s);
 
+// ---- memory-bank adapter (memory.hip) ----
+// the implicit bank: window n = (img, iy, ix) of n_img [C, H, W] images, P x P, stride s
+struct MemGeom {
+  int n_img, C, H, W, P, s, ny, nx;
+  long N;  // n_img * ny * nx
+};
+size_t mem_select_ws_bytes(const MemGeom& g, int B);
+hipError_t launch_mem_select(const float* q, const float* img, const MemGeom& g, int B,
+                             int64_t* idx, void* ws, hipStream_t s);
+hipError_t launch_mem_gather(const float* img, const MemGeom& g, const int64_t* idx, int B,
+                             float* out, hipStream_t s);
+bool memadapter_supported(int C, int HID, int nb);
+long memadapter_param_count(int C, int HID, int nb);
+size_t memadapter_ws_bytes(int N, int C, int H, int W, int HID, int nb, bool bwd);
+hipError_t launch_memadapter_fwd(const float* prm, const float* noisy, const float* base,
+                                 const float* mem, float* out, float* feat, int N, int C, int H,
+                                 int W, int HID, int nb, int clamp, void* ws, hipStream_t s);
+hipError_t launch_memadapter_bwd(const float* prm, const float* noisy, const float* base,
+                                 const float* feat, const float* dout, float* dprm, int N, int C,
+                                 int H, int W, int HID, int nb, int clamp, void* ws, hipStream_t s);
+hipError_t launch_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs,
+                             int ny, int nx, int C, int H, int W, int P, float* out, hipStream_t s);
+
 }  // namespace dn

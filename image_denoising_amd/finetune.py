@@ -224,19 +224,12 @@ def load_base_weights(model: nn.Module, ckpt_path: str):
     return model.load_state_dict(state, strict=False)
 
 
-class FinetuneTrainer:
-    """The finetune.py:269-289 step, fused; returns loss3 = [loss_l1, loss_grad, loss].
+class _AdapterStepBase:
+    """What the adapter finetune steps share: the loss settings, the replicas' broadcast, Adam over
+    the adapter's flat buffer, the step's buffers and the workspace-reusing frozen-base call."""
 
-    lambda_iqsl > 0 makes it the finetune_iqsl.py:469-494 step: `iqsl` = dict(t1, t2[, tau,
-    margin, ce_factor]) (the thresholds from `estimate_intensity_thresholds`), and the step returns
-    loss4 = [loss_l1, loss_grad, loss_iqsl, loss].  Each rank's loss is the mean over its own
-    batch, as an nn.DataParallel replica computes it."""
-
-    def __init__(self, model: DenoiserWithAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
-                 distributed: bool | None = None, lambda_iqsl: float = 0.0,
-                 iqsl: dict | None = None):
-        if not isinstance(model, DenoiserWithAdapter):
-            raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
+    def __init__(self, model, lr: float, lambda_grad: float, distributed: bool | None,
+                 lambda_iqsl: float, iqsl: dict | None):
         self.model = model
         self.lambda_grad = lambda_grad
         self.lambda_iqsl = float(lambda_iqsl)
@@ -277,6 +270,32 @@ class FinetuneTrainer:
             with torch.no_grad():
                 out.copy_(base(noisy))
 
+    def _loss(self, pred, clean):
+        """(loss4, dpred) with IQSL, else (loss3, dpred)"""
+        if self.iqsl is not None:
+            return finetune_iqsl_loss(pred, clean, self.lambda_grad, self.lambda_iqsl, **self.iqsl)
+        return finetune_loss(pred, clean, self.lambda_grad)
+
+    def _update(self):
+        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
+        self.opt.step(self.grad, grad_scale=scale)
+
+
+class FinetuneTrainer(_AdapterStepBase):
+    """The finetune.py:269-289 step, fused; returns loss3 = [loss_l1, loss_grad, loss].
+
+    lambda_iqsl > 0 makes it the finetune_iqsl.py:469-494 step: `iqsl` = dict(t1, t2[, tau,
+    margin, ce_factor]) (the thresholds from `estimate_intensity_thresholds`), and the step returns
+    loss4 = [loss_l1, loss_grad, loss_iqsl, loss].  Each rank's loss is the mean over its own
+    batch, as an nn.DataParallel replica computes it."""
+
+    def __init__(self, model: DenoiserWithAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
+                 distributed: bool | None = None, lambda_iqsl: float = 0.0,
+                 iqsl: dict | None = None):
+        if not isinstance(model, DenoiserWithAdapter):
+            raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
+        super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl)
+
     def train_step(self, clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
         clean, noisy = clean.contiguous(), noisy.contiguous()
         if clean.shape != noisy.shape:
@@ -285,12 +304,7 @@ class FinetuneTrainer:
         b = self._buffers(noisy.shape, noisy.device)
         self._base_forward(noisy, b["base"])
         ad._run_forward(noisy, b["base"], b["pred"])
-        if self.iqsl is not None:
-            loss3, dpred = finetune_iqsl_loss(b["pred"], clean, self.lambda_grad, self.lambda_iqsl,
-                                              **self.iqsl)
-        else:
-            loss3, dpred = finetune_loss(b["pred"], clean, self.lambda_grad)
+        loss3, dpred = self._loss(b["pred"], clean)
         ad._run_backward(noisy, b["base"], dpred, self.grad)
-        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
-        self.opt.step(self.grad, grad_scale=scale)
+        self._update()
         return loss3

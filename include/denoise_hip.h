@@ -535,6 +535,49 @@ dn_status dn_resnet_backward_prec(const dn_unet_cfg* cfg, const float* params, c
 dn_status dn_resnet_debug_buffers(const dn_unet_cfg* cfg, int N, int H, int W, int with_backward,
                                   int64_t* desc, int max_entries, int* n_entries);
 
+/* ---- memory-bank adapter: finetune_memory.py, evaluation_704_iqsl_memory.py ---------------------
+   The bank is IMPLICIT: n_img paired noisy / clean images [n_img, C, H, W] (fp32, NCHW); patch
+   n = img * ny * nx + iy * nx + ix is the P x P window at (iy * stride, ix * stride), ny =
+   (H - P) / stride + 1, nx = (W - P) / stride + 1 -- F.unfold's order, images concatenated.
+   C is 1 or 3, P >= 3, stride >= 1, H, W >= P. */
+size_t dn_memory_select_ws_size(int B, int n_img, int C, int H, int W, int P, int stride);
+/* idx[b] = argmin_n sum (queries[b] - noisy patch n)^2, fp32, ties to the lowest n; queries
+   [B, C, P, P].  Two stages (distance shares per window, then their sum and the argmin per
+   query) in a fixed order, no atomics, no host read. */
+dn_status dn_memory_select(const float* queries, const float* noise_images, int B, int n_img, int C,
+                           int H, int W, int P, int stride, int64_t* idx, void* ws,
+                           size_t ws_bytes, void* stream);
+/* out[b] = clean patch idx[b]   ([B, C, P, P]) */
+dn_status dn_memory_gather(const float* clean_images, const int64_t* idx, int B, int n_img, int C,
+                           int H, int W, int P, int stride, float* out, void* stream);
+/* HyperGatedResidualAdapter_FFT (num_fft_bins = 0: HyperGatedResidualAdapter).  Parameters: one
+   flat fp32 buffer in state_dict order -- local_net.0.weight [Hc,2C,3,3], .0.bias, local_net.2.weight
+   [Hc,Hc,3,3], .2.bias, local_net.4.weight [C,Hc,3,3], .4.bias, hyper_mlp.0.weight [Hc, 6 + 3 nb],
+   .0.bias, hyper_mlp.2.weight [2C, Hc], .2.bias.  C is 1 or 3, Hc 8 or 16, nb <= 8. */
+dn_status dn_memadapter_param_count(int in_channels, int hidden_channels, int num_fft_bins,
+                                    size_t* count);
+/* bytes of workspace of the forward (with_backward = 0) or the backward (0 = unsupported) */
+size_t dn_memadapter_ws_size(int N, int C, int H, int W, int hidden_channels, int num_fft_bins,
+                             int with_backward);
+/* features [N, 6 + 3 nb] = mean / unbiased std of noisy, base_out, mem_clean, then their row-DFT
+   band features (fp64 inside); out = clamp(base_out + gamma * local_net(cat[noisy, base_out]) +
+   beta, 0, 1) (no clamp if clamp_output == 0).  Any W with W / 2 + 1 >= nb; C * H * W >= 2. */
+dn_status dn_memadapter_forward(const float* params, const float* noisy, const float* base_out,
+                                const float* mem_clean, float* out, float* features, int N, int C,
+                                int H, int W, int hidden_channels, int num_fft_bins,
+                                int clamp_output, void* ws, size_t ws_bytes, void* stream);
+/* dparams = dL/dparams for dout = dL/dout, from the forward's features (constants of the
+   gradient).  Overwrites dparams; fixed summation order. */
+dn_status dn_memadapter_backward(const float* params, const float* noisy, const float* base_out,
+                                 const float* features, const float* dout, float* dparams, int N,
+                                 int C, int H, int W, int hidden_channels, int num_fft_bins,
+                                 int clamp_output, void* ws, size_t ws_bytes, void* stream);
+/* Patchwise inference's blend: pred [ny * nx, C, P, P] are the patches at origins (ys[iy], xs[ix])
+   (device int32), hann the 1-D window [P]; out [C, H, W] = sum pred * w / (sum w + 1e-8), w =
+   max(hann[py] * hann[px], 1e-3), each pixel's patches added in the order iy, ix. */
+dn_status dn_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs, int ny,
+                        int nx, int C, int H, int W, int P, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
