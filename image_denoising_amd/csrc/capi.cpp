@@ -24,6 +24,20 @@ dn_status hip_status(hipError_t e, const char* what) {
   return fail(DN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// The workspace's size decides a forward's plan: one sized with_backward=1 gets that plan (the
+// forward saves what the backward reads); a smaller one, or !bwd_ok, gets the forward-only plan.
+template <class P, class Build>
+dn_status plan_for_workspace(Build build, const dn_unet_cfg& cfg, int N, int H, int W,
+                             size_t ws_bytes, bool bwd_ok, const char* size_fn, P& p) {
+  std::string err;
+  if (!bwd_ok || !build(cfg, N, H, W, true, p, err) ||
+      ws_bytes < (size_t)p.total_floats * sizeof(float))
+    if (!build(cfg, N, H, W, false, p, err)) return fail(DN_ERR_ARG, err);
+  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
+    return fail(DN_ERR_WORKSPACE, std::string("workspace smaller than ") + size_fn + "()");
+  return DN_OK;
+}
+
 #define DN_GUARD_BEGIN try {
 #define DN_GUARD_END                                              \
   }                                                               \
@@ -110,6 +124,18 @@ dn_status dn_unet_workspace_size(const dn_unet_cfg* cfg, int N, int H, int W, in
   DN_GUARD_END
 }
 
+// the plan a UNet forward entry point runs on this workspace (bf16: the forward-only plan)
+static dn_status forward_plan(const dn_unet_cfg* cfg, int N, int H, int W, size_t ws_bytes,
+                              int precision, Plan& p) {
+  if (precision != DN_PREC_FP32 && precision != DN_PREC_FP32_X6 && precision != DN_PREC_BF16)
+    return fail(DN_ERR_ARG, "unknown precision");
+  const bool bwd_ok = precision != DN_PREC_BF16;
+  const dn_status st = plan_for_workspace(build_plan, *cfg, N, H, W, ws_bytes, bwd_ok,
+                                          "dn_unet_workspace_size", p);
+  if (st == DN_OK && !bwd_ok) p.with_bwd = false;
+  return st;
+}
+
 dn_status dn_unet_forward(const dn_unet_cfg* cfg, const float* params, const float* x, float* y,
                           int N, int H, int W, void* ws, size_t ws_bytes, void* stream) {
   return dn_unet_forward_prec(cfg, params, x, y, N, H, W, ws, ws_bytes, DN_PREC_FP32, stream);
@@ -125,36 +151,10 @@ dn_status dn_unet_forward_prec(const dn_unet_cfg* cfg, const float* params, cons
     return fail(DN_ERR_ARG, "unknown precision");
   if (!cfg || !params || !x || !y || !ws) return fail(DN_ERR_ARG, "null argument");
   Plan p;
-  std::string err;
-  // The workspace's size decides the plan: one sized with_backward=1 gets the backward plan
-  // (dense concat strides, the layout dn_unet_backward reads) and the forward saves the
-  // activations the backward needs (the fused head writes d1b/na/nb); a smaller one gets the
-  // forward-only plan, whose concat strides are padded to 128-B lines (a different layout).
-  if (!build_plan(*cfg, N, H, W, true, p, err)) return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float) &&
-      !build_plan(*cfg, N, H, W, false, p, err))
-    return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
-    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_unet_workspace_size()");
+  // (with-backward plan: dense concat strides; forward-only: strides padded to 128-B lines)
+  if (dn_status st = forward_plan(cfg, N, H, W, ws_bytes, precision, p)) return st;
   return unet_forward(p, params, x, y, static_cast<float*>(ws), (hipStream_t)stream, precision);
   DN_GUARD_END
-}
-
-// the plan a forward entry point runs on this workspace (dn_unet_forward_prec's rule; bf16:
-// the forward-only plan)
-static dn_status forward_plan(const dn_unet_cfg* cfg, int N, int H, int W, size_t ws_bytes,
-                              int precision, Plan& p) {
-  std::string err;
-  if (precision != DN_PREC_FP32 && precision != DN_PREC_FP32_X6 && precision != DN_PREC_BF16)
-    return fail(DN_ERR_ARG, "unknown precision");
-  const bool bwd_ok = precision != DN_PREC_BF16;
-  if (!bwd_ok || !build_plan(*cfg, N, H, W, true, p, err) ||
-      ws_bytes < (size_t)p.total_floats * sizeof(float))
-    if (!build_plan(*cfg, N, H, W, false, p, err)) return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
-    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_unet_workspace_size()");
-  if (!bwd_ok) p.with_bwd = false;
-  return DN_OK;
 }
 
 dn_status dn_unet_pack_weights(const dn_unet_cfg* cfg, const float* params, int N, int H, int W,
@@ -350,14 +350,9 @@ dn_status dn_resnet_forward_prec(const dn_unet_cfg* cfg, const float* params, co
     return fail(DN_ERR_ARG, "RESNET precision must be DN_PREC_FP32 or DN_PREC_FP32_X6");
   if (!cfg || !params || !x || !y || !ws) return fail(DN_ERR_ARG, "null argument");
   ResPlan p;
-  std::string err;
-  // the workspace's size decides the plan, as in dn_unet_forward_prec
-  if (!res_build_plan(*cfg, N, H, W, true, p, err)) return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float) &&
-      !res_build_plan(*cfg, N, H, W, false, p, err))
-    return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
-    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_resnet_workspace_size()");
+  if (dn_status st = plan_for_workspace(res_build_plan, *cfg, N, H, W, ws_bytes, true,
+                                        "dn_resnet_workspace_size", p))
+    return st;
   return resnet_forward(p, params, x, y, static_cast<float*>(ws), (hipStream_t)stream, precision);
   DN_GUARD_END
 }
@@ -1082,15 +1077,10 @@ dn_status dn_iunet_forward_prec(const dn_unet_cfg* cfg, const float* params, con
     return fail(DN_ERR_ARG, "ImprovedUNet precision must be DN_PREC_FP32 or DN_PREC_FP32_X6");
   if (!cfg || !params || !x || !y || !ws) return fail(DN_ERR_ARG, "null argument");
   IPlan p;
-  std::string err;
-  // the plan with the backward buffers has the same forward offsets: a workspace that large
-  // makes the forward keep what the backward reads
-  if (!iunet_build_plan(*cfg, N, H, W, true, p, err)) return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float) &&
-      !iunet_build_plan(*cfg, N, H, W, false, p, err))
-    return fail(DN_ERR_ARG, err);
-  if (ws_bytes < (size_t)p.total_floats * sizeof(float))
-    return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_iunet_workspace_size()");
+  // (the plan with the backward buffers has the same forward offsets)
+  if (dn_status st = plan_for_workspace(iunet_build_plan, *cfg, N, H, W, ws_bytes, true,
+                                        "dn_iunet_workspace_size", p))
+    return st;
   return iunet_forward(p, params, x, y, static_cast<float*>(ws), (hipStream_t)stream, precision);
   DN_GUARD_END
 }

@@ -40,13 +40,6 @@ struct OpTimer {
   OpTimer& operator=(const OpTimer&) = delete;
 };
 
-// DN_TRY(call) bracketed by an OpTimer (statement form)
-#define DN_TIMED(st, op, flops, K, NO, h, w, n, call)          \
-  do {                                                        \
-    const ::dn::OpTimer dn_timer_(st, op, flops, K, NO, h, w, n); \
-    DN_TRY(call);                                             \
-  } while (0)
-
 // How an output pixel of the implicit-GEMM kernel gathers its input pixels.
 enum Gather {
   G_C3 = 0,   // 3x3, stride 1, pad 1: in(y+ky-1, x+kx-1), 9 taps     (conv fwd / conv dgrad)

@@ -18,22 +18,13 @@
 //   y = sigmoid(final([x_up3 | x]))                      arch_unet.py:530-531
 #include <algorithm>
 
+#include "exec_common.h"
 #include "iunet.h"
 #include "iunet_ops.h"
-#include "unet.h"
 
 namespace dn {
 
 namespace {
-
-#define IU_TRY(x)                                                         \
-  do {                                                                    \
-    hipError_t e_ = (x);                                                  \
-    if (e_ != hipSuccess) {                                               \
-      set_error(std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_)); \
-      return DN_ERR_HIP;                                                  \
-    }                                                                     \
-  } while (0)
 
 constexpr int GROWTH = 32;  // RDB growth (arch_unet.py:437)
 constexpr float GN_EPS = 1e-5f;
@@ -202,9 +193,9 @@ dn_status gn_forward(const View& z, int N, long P, int C, int G, const float* ga
                      const float* beta, int act, const View* res, const View& y, float* stats,
                      double* part, float* scale, float* shift, hipStream_t s) {
   const int S = chan_sums_splits(N, P);
-  IU_TRY(launch_chan_sums(z, nullptr, N, P, C, S, part, s));
-  IU_TRY(launch_gn_fwd_fin(part, S, N, C, G, P, GN_EPS, gamma, beta, stats, scale, shift, s));
-  IU_TRY(launch_affine(z, nullptr, scale, nullptr, shift, act, res, y, N, P, C, s));
+  DN_TRY(launch_chan_sums(z, nullptr, N, P, C, S, part, s));
+  DN_TRY(launch_gn_fwd_fin(part, S, N, C, G, P, GN_EPS, gamma, beta, stats, scale, shift, s));
+  DN_TRY(launch_affine(z, nullptr, scale, nullptr, shift, act, res, y, N, P, C, s));
   return DN_OK;
 }
 
@@ -212,9 +203,9 @@ dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G
                       const float* gamma, const float* stats, const View& dz, float* dgamma,
                       float* dbeta, double* part, float* ca, float* cb, float* cc, hipStream_t s) {
   const int S = chan_sums_splits(N, P);
-  IU_TRY(launch_chan_sums(dy, &z, N, P, C, S, part, s));
-  IU_TRY(launch_gn_bwd_fin(part, S, N, C, G, P, gamma, stats, ca, cb, cc, dgamma, dbeta, s));
-  IU_TRY(launch_affine(dy, &z, ca, cb, cc, 0, nullptr, dz, N, P, C, s));
+  DN_TRY(launch_chan_sums(dy, &z, N, P, C, S, part, s));
+  DN_TRY(launch_gn_bwd_fin(part, S, N, C, G, P, gamma, stats, ca, cb, cc, dgamma, dbeta, s));
+  DN_TRY(launch_affine(dy, &z, ca, cb, cc, 0, nullptr, dz, N, P, C, s));
   return DN_OK;
 }
 
@@ -239,15 +230,15 @@ dn_status gwgrad_run(int mode, const View& g, const View& x, int N, int h, int w
   a.zeros = slab; a.slab = slab + 64; a.slab_stride = n;
   a.wlayout = 0; a.cin_total = cin; a.ci_base = 0; a.bias = bias ? 1 : 0;
   int sp = gwgrad_splits(mode, N, h, w, cin, cout);
-  IU_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s));
+  DN_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s));
   // fp32_x6: the 3x3 weight gradients on the bf16x6 kernel too
   if (prec == DN_PREC_FP32_X6 && mode == W_C3 && gwgrad_x6_ok(a)) {
     sp = gwgrad_x6_splits(a, sp);
-    IU_TRY(launch_gwgrad_x6(a, sp, s));
+    DN_TRY(launch_gwgrad_x6(a, sp, s));
   } else {
-    IU_TRY(launch_gwgrad(mode, a, sp, s));
+    DN_TRY(launch_gwgrad(mode, a, sp, s));
   }
-  IU_TRY(launch_reduce(slab + 64, n, sp, n, dwb, s));
+  DN_TRY(launch_reduce(slab + 64, n, sp, n, dwb, s));
   return DN_OK;
 }
 
@@ -495,7 +486,7 @@ struct Ctx {
   float* ws;
   hipStream_t s;
   int prec;
-  SideStream* side;  // backward: the weight gradients' stream and fork event (nullptr: all on s)
+  BwdStreams* bs;  // backward: the weight gradients' stream and its fork (s2 == s on one stream)
   View V(long o, int stride, int off = 0) const { return View{ws + o, stride, off}; }
   View V(const IView& v) const { return v.o < 0 ? kNone : View{ws + v.o, v.stride, v.off}; }
   const ISite& site(const IConv& c) const { return p.site[c.idx]; }
@@ -564,9 +555,9 @@ dn_status pack_images(const Ctx& c, bool bwd) {
       set_error("ImprovedUNet: no weight image for a conv");
       return DN_ERR_ARG;
     }
-    IU_TRY(pack_add(pb, j, c.s));
+    DN_TRY(pack_add(pb, j, c.s));
   }
-  IU_TRY(pack_flush(pb, c.s));
+  DN_TRY(pack_flush(pb, c.s));
   return DN_OK;
 }
 
@@ -579,7 +570,7 @@ dn_status conv_fwd(const Ctx& c, const IConv& L) {
   const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
   const OpTimer timer(c.s, L.k == 3 ? "fwd3" : "fwd1", conv_flops(N, h, w, L.cout, L.cin, L.k),
                       L.cin, L.cout, h, w, N);
-  IU_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.in), N, h, w, L.cin, L.cout, c.Bs(L), s.epi,
+  DN_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.in), N, h, w, L.cin, L.cout, c.Bs(L), s.epi,
                   c.V(s.out), s.layout, c.V(s.aux), c.s));
   return DN_OK;
 }
@@ -590,7 +581,7 @@ dn_status dgrad_g(const Ctx& c, const IConv& L) {
   const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
   const OpTimer timer(c.s, L.k == 3 ? "dgrad3" : "dgrad1", conv_flops(N, h, w, s.nout, L.cout, L.k),
                       L.cout, s.nout, h, w, N);
-  IU_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.g), N, h, w, L.cout, s.nout, nullptr, s.depi,
+  DN_TRY(run_conv(c.R.r[L.idx], c.image(L), c.V(s.g), N, h, w, L.cout, s.nout, nullptr, s.depi,
                   c.V(s.dx), OUT_NHWC, c.V(s.daux), c.s));
   return DN_OK;
 }
@@ -600,8 +591,8 @@ dn_status wgrad_g(const Ctx& c, float* dprm, const IConv& L) {
   const ISite& s = c.site(L);
   const int N = c.p.N, h = c.p.H >> s.lvl, w = c.p.W >> s.lvl;
   // on the side stream, behind the main stream's work so far (g is its latest output)
-  const hipStream_t s2 = c.side ? c.side->st : c.s;
-  IU_TRY(side_fork(c.side, c.s));
+  const hipStream_t s2 = c.bs->s2;
+  DN_TRY(c.bs->fork());
   const OpTimer timer(s2, L.k == 3 ? "wgrad3" : "wgrad1", conv_flops(N, h, w, L.cout, L.cin, L.k),
                       L.cin, L.cout, h, w, N);
   const int taps = s.wmode == W_C3 ? 9 : 1;
@@ -665,17 +656,17 @@ dn_status forward_body(const Ctx& c, const float* x, float* y) {
   const IParams& P = p.P;
   const int N = p.N, H = p.H, W = p.W, C = P.C;
   // noise estimator: h = leaky(ne0(x)) (also writes x into x0[:, :C], zeros x0[:, C:4])
-  IU_TRY(launch_enc0_fwd(x, N, C, H, W, prm + P.ne0.w, prm + P.ne0.b, ws + p.h, ws + p.x0, 4, 0, 4,
+  DN_TRY(launch_enc0_fwd(x, N, C, H, W, prm + P.ne0.w, prm + P.ne0.b, ws + p.h, ws + p.x0, 4, 0, 4,
                          nullptr, s));
-  IU_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48), prm + P.ne2.b,
+  DN_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48), prm + P.ne2.b,
                            TE_SIGMOID, kNone, c.V(p.x0, 4, C), 0, 1, s));
   if (p.with_bwd) {
-    IU_TRY(hipMemcpyAsync(ws + p.xin, x, sizeof(float) * (size_t)N * C * H * W,
+    DN_TRY(hipMemcpyAsync(ws + p.xin, x, sizeof(float) * (size_t)N * C * H * W,
                           hipMemcpyDeviceToDevice, s));
-    IU_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48),
+    DN_TRY(launch_conv3_thin(c.V(p.h, 48), N, H, W, 48, thin_view(prm + P.ne2.w, 48),
                              prm + P.ne2.b, TE_SIGMOID, kNone, View{ws + p.sig, 0, 0}, 1, 1, s));
   }
-  IU_TRY(launch_nchw_to_slice(x, N, C, H, W, ws + p.cf, 28, 24, 28, s));  // final concat input
+  DN_TRY(launch_nchw_to_slice(x, N, C, H, W, ws + p.cf, 28, 24, 28, s));  // final concat input
   // encoder
   for (int i = 0; i < 4; ++i) {
     const ILevel& L = P.down[i];
@@ -686,7 +677,7 @@ dn_status forward_body(const Ctx& c, const float* x, float* y) {
     const View skip = c.V(p.cc[k], 3 * out, out);
     if (dn_status st = res_fwd(c, L.res, p.dl[i], h, w, skip)) return st;
     const View dst = i < 3 ? c.V(p.pool[i + 1], nf) : c.V(p.bb.F, 384 + 4 * GROWTH);
-    IU_TRY(launch_vpool_fwd(skip, N, h, w, nf, dst, s));
+    DN_TRY(launch_vpool_fwd(skip, N, h, w, nf, dst, s));
   }
   // bottleneck
   if (dn_status st = rdb_fwd(c, P.brdb)) return st;
@@ -701,10 +692,10 @@ dn_status forward_body(const Ctx& c, const float* x, float* y) {
     const View o = k < 3 ? c.V(p.xu[k], u.out) : c.V(p.cf, 28);
     if (dn_status st = res_fwd(c, u.res, p.ul[k], h, w, o)) return st;
   }
-  IU_TRY(launch_conv3_thin(c.V(p.cf, 28), N, H, W, 24 + C, thin_view(prm + P.fin.w, 24 + C),
+  DN_TRY(launch_conv3_thin(c.V(p.cf, 28), N, H, W, 24 + C, thin_view(prm + P.fin.w, 24 + C),
                            prm + P.fin.b, TE_SIGMOID, kNone, View{y, 0, 0}, 1, P.OC, s));
   if (p.with_bwd)
-    IU_TRY(hipMemcpyAsync(ws + p.yout, y, sizeof(float) * (size_t)N * P.OC * H * W,
+    DN_TRY(hipMemcpyAsync(ws + p.yout, y, sizeof(float) * (size_t)N * P.OC * H * W,
                           hipMemcpyDeviceToDevice, s));
   return DN_OK;
 }
@@ -748,10 +739,10 @@ dn_status rdb_bwd(const Ctx& c, float* dprm, const IRdb& R, const IBlockBufs& b,
   const long npx = (long)c.p.N * h * w;
   if (dn_status st = wgrad_g(c, dprm, R.lff)) return st;
   if (dn_status st = dgrad_g(c, R.lff)) return st;
-  IU_TRY(launch_vadd(c.V(b.dF, FS), c.V(b.dr, C), npx, C, c.s));  // out = x + lff(...)
+  DN_TRY(launch_vadd(c.V(b.dF, FS), c.V(b.dr, C), npx, C, c.s));  // out = x + lff(...)
   for (int j = 3; j >= 0; --j) {
     const int o = C + GROWTH * j;
-    IU_TRY(launch_vmask(c.V(b.dzj[j], GROWTH), c.V(b.dF, FS, o), c.V(b.F, FS, o), npx, GROWTH, c.s));
+    DN_TRY(launch_vmask(c.V(b.dzj[j], GROWTH), c.V(b.dF, FS, o), c.V(b.F, FS, o), npx, GROWTH, c.s));
     if (dn_status st = wgrad_g(c, dprm, R.conv[j])) return st;
     if (dn_status st = dgrad_g(c, R.conv[j])) return st;
   }
@@ -763,15 +754,15 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
   const float* prm = c.prm;
   float* ws = c.ws;
   const hipStream_t s = c.s;
-  const hipStream_t s2 = c.side ? c.side->st : s;
+  const hipStream_t s2 = c.bs->s2;
   const IParams& P = p.P;
   const int N = p.N, H = p.H, W = p.W, C = P.C, OC = P.OC;
   const long HW = (long)H * W;
   // final: dz = dy * y(1-y)  (stride-4 NHWC), then its weight / data gradients
-  IU_TRY(launch_dsigmoid_nchw(ws + p.yout, dy, N, OC, HW, ws + p.dzfin, 4, s));
+  DN_TRY(launch_dsigmoid_nchw(ws + p.yout, dy, N, OC, HW, ws + p.dzfin, 4, s));
   if (dn_status st = wgrad_g(c, dprm, P.fin)) return st;
   // gradient of x_up3 = the first 24 channels of the final concat (the input slice needs none)
-  IU_TRY(hipMemsetAsync(ws + p.dsg, 0, sizeof(float) * 4 * (size_t)N * HW, s));
+  DN_TRY(hipMemsetAsync(ws + p.dsg, 0, sizeof(float) * 4 * (size_t)N * HW, s));
   if (dn_status st = dgrad_g(c, P.fin)) return st;
   // decoder, last block first
   for (int k = 3; k >= 0; --k) {
@@ -781,11 +772,11 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
     if (dn_status st = res_bwd(c, dprm, u.res, b, h, w)) return st;
     if (dn_status st = rdb_bwd(c, dprm, u.rdb, b, h, w)) return st;
     // f = leaky(fuse(cc)): dz = dF[:, :out] * leaky'(f)
-    IU_TRY(launch_vmask(c.V(b.dzf, out), c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, out, s));
+    DN_TRY(launch_vmask(c.V(b.dzf, out), c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, out, s));
     if (dn_status st = wgrad_g(c, dprm, u.fuse)) return st;
     if (dn_status st = dgrad_g(c, u.fuse)) return st;
     // PixelShuffle backward, then conv_ps (input: bottle output or the previous up block)
-    IU_TRY(launch_unshuffle(c.V(p.dcc[k], 3 * out), N, h / 2, w / 2, out, ws + p.dps[k], s));
+    DN_TRY(launch_unshuffle(c.V(p.dcc[k], 3 * out), N, h / 2, w / 2, out, ws + p.dps[k], s));
     if (dn_status st = wgrad_g(c, dprm, u.ps)) return st;
     if (dn_status st = dgrad_g(c, u.ps)) return st;
   }
@@ -801,11 +792,11 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
     const int k = 3 - i, out = P.up[k].out;
     const View skip = c.V(p.cc[k], 3 * out, out), dskip = c.V(p.dcc[k], 3 * out, out);
     // d s_i = (skip gradient from the fuse conv) + maxpool backward of d x_{i+1}
-    IU_TRY(launch_vpool_bwd_acc(skip, N, h, w, nf, dpooled, dskip, s));
+    DN_TRY(launch_vpool_bwd_acc(skip, N, h, w, nf, dpooled, dskip, s));
     if (dn_status st = res_bwd(c, dprm, L.res, b, h, w)) return st;
     if (dn_status st = rdb_bwd(c, dprm, L.rdb, b, h, w)) return st;
     const View dza = c.V(p.dza[i], nf);
-    IU_TRY(launch_vmask(dza, c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, nf, s));
+    DN_TRY(launch_vmask(dza, c.V(b.dF, FS), c.V(b.F, FS), (long)N * h * w, nf, s));
     if (i > 0) {
       if (dn_status st = wgrad_g(c, dprm, L.conv)) return st;
       if (dn_status st = dgrad_g(c, L.conv)) return st;
@@ -816,17 +807,17 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
       float* slab = ws + p.slab;
       const long n = 48L * (C + 1) * 9 + 48;
       const int st = enc0_wgrad_splits(N, H, W);
-      IU_TRY(side_fork(c.side, s));
-      IU_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.xin, N, C, H, W, slab, n, C + 1, 0, 1,
+      DN_TRY(c.bs->fork());
+      DN_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.xin, N, C, H, W, slab, n, C + 1, 0, 1,
                                   st, s2));
-      IU_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.sig, N, 1, H, W, slab, n, C + 1, C, 0,
+      DN_TRY(launch_wgrad_c3_thin(ws + p.dza[0], 48, ws + p.sig, N, 1, H, W, slab, n, C + 1, C, 0,
                                   st, s2));
-      IU_TRY(launch_reduce(slab, n, st, n, dprm + L.conv.w, s2));
+      DN_TRY(launch_reduce(slab, n, st, n, dprm + L.conv.w, s2));
       // d sigma (channel C of x0) through the sigmoid: flipped weight column ci = C
       WView fv{};
       fv.w = prm + L.conv.w; fv.off = (long)C * 9; fv.sN = 9; fv.sK = (long)(C + 1) * 9;
       fv.sT = 1; fv.taps = 9; fv.flip = 1;
-      IU_TRY(launch_conv3_thin(dza, N, H, W, 48, fv, nullptr, TE_DSIG, c.V(p.x0, 4, C),
+      DN_TRY(launch_conv3_thin(dza, N, H, W, 48, fv, nullptr, TE_DSIG, c.V(p.x0, 4, C),
                                c.V(p.dsg, 4), 0, 1, s));
     }
   }
@@ -837,14 +828,12 @@ dn_status backward_body(const Ctx& c, const float* dy, float* dprm) {
     float* slab = ws + p.slab;
     const long n = 48L * C * 9 + 48;
     const int st = enc0_wgrad_splits(N, H, W);
-    IU_TRY(side_fork(c.side, s));
-    IU_TRY(launch_wgrad_c3_thin(ws + p.dh, 48, ws + p.xin, N, C, H, W, slab, n, C, 0, 1, st, s2));
-    IU_TRY(launch_reduce(slab, n, st, n, dprm + P.ne0.w, s2));
+    DN_TRY(c.bs->fork());
+    DN_TRY(launch_wgrad_c3_thin(ws + p.dh, 48, ws + p.xin, N, C, H, W, slab, n, C, 0, 1, st, s2));
+    DN_TRY(launch_reduce(slab, n, st, n, dprm + P.ne0.w, s2));
   }
-  if (c.side) {  // the caller's stream continues after every weight gradient
-    IU_TRY(hipEventRecord(c.side->join, s2));
-    IU_TRY(hipStreamWaitEvent(s, c.side->join, 0));
-  }
+  // the caller's stream continues after every weight gradient (nothing ran on the reduction stream)
+  DN_TRY(c.bs->join(/*reductions=*/false));
   return DN_OK;
 }
 
@@ -859,10 +848,10 @@ dn_status iunet_backward(const IPlan& p, const float* prm, const float* dy, floa
   // the launch that produced its output gradient; every buffer one reads (the forward's
   // activations, dz2 / dz1 / dr / dzf of a block, dzj[j], dps[k], dza[i], dzfin, dsg, dh once
   // written) is not rewritten later in the pass, and only they use the slab.  Joined at the end.
-  SideStream* side = bwd_two_streams() && !prof_on() ? side_stream(s) : nullptr;
+  BwdStreams bs(s);
   IRoutes R;
   if (dn_status st = iunet_bwd_routes(p, prec, R)) return st;
-  const Ctx c{p, R, prm, ws, s, prec, side};
+  const Ctx c{p, R, prm, ws, s, prec, &bs};
   if (dn_status st = pack_images(c, true)) return st;
   return backward_body(c, dy, dprm);
 }

@@ -2,6 +2,7 @@
 // workspace plan and the forward / backward launch sequences, in the shape of unet.cpp: a plan,
 // the kernel routes of a pass resolved once, one pack launch, then the run.  Every layer runs at
 // the input resolution (any H, W >= 1); the concatenations are placements into strided slices.
+// The op helpers, the backward's streams and the tail shared with the UNet: exec_common.{h,cpp}.
 #include "resnet.h"
 
 #include <cstdlib>
@@ -152,19 +153,11 @@ bool res_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, ResPlan
       p.slab[i] = -1;
       if (i == R_UP5) continue;  // no gradient: its range of dparams is zeroed
       const int mode = L.k == 3 ? W_C3 : W_C1;
-      const int sp = i == R_ENC0 ? enc0_wgrad_splits(N, H, W)
-                     : i == R_NINC ? wgrad_thin_splits(px)
-                                   : wgrad_splits(mode, N, H, W, i == R_D1A ? 2 * nf : L.cin, L.cout);
-      p.splits[i] = sp;
-      long need = (i == R_ENC0 || i == R_D1A || i == R_NINC)
-                      ? (long)sp * (L.wcount + L.cout)
-                      : wgrad_slab_floats(mode, N, H, W, L.cin, L.cout);
-      if (i == R_NINC) {  // also the rows nin_b's k_wgrad1p<., GNB> writes nin_c's gradient into
-        const long s1 = wgrad1_splits(W_C1, N, H, W);
-        if (s1 * (L.wcount + L.cout) > need) need = s1 * (L.wcount + L.cout);
-      }
-      if (i == R_D1A) need += (long)enc0_wgrad_splits(N, H, W) * 96 * p.C * 9;  // input slice
-      p.slab[i] = alloc_f(64 + need);
+      const int kind = i == R_ENC0 ? SLAB_ENC0 : i == R_D1A ? SLAB_D1A
+                       : i == R_NINC ? SLAB_NINC_THIN : SLAB_CONV;  // (out_nc <= 4 always)
+      const WgradSlab sl = plan_wgrad_slab(kind, mode, N, H, W, L, p.C);
+      p.splits[i] = sl.splits;
+      p.slab[i] = alloc_f(64 + sl.floats);
     }
   }
   p.total_floats = off;
@@ -172,24 +165,13 @@ bool res_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, ResPlan
   return true;
 }
 
-#define DN_TRY(x)                                                         \
-  do {                                                                    \
-    hipError_t e_ = (x);                                                  \
-    if (e_ != hipSuccess) {                                               \
-      set_error(std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_)); \
-      return DN_ERR_HIP;                                                  \
-    }                                                                     \
-  } while (0)
-
 // ------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------
 namespace {
 
-enum ResKind { RK_F32, RK_X6 };  // conv on the fp32 kernel (packF / packB) | the bf16x6 kernels
-struct ResRoute { int kind; long img; int tail; int zc; long wp_z; };
 struct ResRoutes {
-  ResRoute r[R_NL];  // enc_conv1 .. dec_conv1b
+  ConvRoute r[R_NL];  // enc_conv1 .. dec_conv1b: CV_F32 (packF / packB) | CV_X6 (packX / packXB)
   bool head_x6;      // the nin head (forward) / its data gradients (backward) in bf16x6
 };
 
@@ -199,14 +181,12 @@ ResRoutes res_fwd_routes(const ResPlan& p, int prec) {
   for (int i = R_ENC1; i <= R_D1B; ++i) {
     if (i == R_UP5) continue;
     const Layer& L = p.P.L[i];
-    ResRoute& r = R.r[i];
+    ConvRoute& r = R.r[i] = ConvRoute{CV_F32, p.packF[i]};
     if (x6 && p.packX[i] >= 0) {
       // dec_conv1a reads [d2b | x | zero pad]: the pad channels as reduction channels with zero
       // packed weights keep K % 4 == 0 (as the UNet's dec_conv1a)
-      r.kind = RK_X6; r.img = p.packX[i];
+      r.kind = CV_X6; r.img = p.packX[i];
       r.tail = x6_image_mode(p.N, p.H, p.W, i == R_D1A ? p.c1kp : L.cin, L.cout, 0, true);
-    } else {
-      r.kind = RK_F32; r.img = p.packF[i];
     }
   }
   R.head_x6 = x6 && p.C <= X6_HEAD_OCMAX;
@@ -218,17 +198,7 @@ ResRoutes res_bwd_routes(const ResPlan& p, int prec) {
   ResRoutes B{};
   for (int i = R_ENC1; i <= R_D1B; ++i) {
     if (i == R_UP5) continue;
-    const Layer& L = p.P.L[i];
-    ResRoute& r = B.r[i];
-    if (x6 && p.packXB[i] >= 0) {
-      const int nout = res_dgrad_nout(p, i);
-      r.kind = RK_X6; r.img = p.packXB[i];
-      r.zc = x6_dgrad_zc(nout);
-      r.wp_z = x6_wp_z(L.cout, nout, r.zc);
-      r.tail = x6_image_mode(p.N, p.H, p.W, L.cout, nout, r.zc, true);
-    } else {
-      r.kind = RK_F32; r.img = p.packB[i];
-    }
+    B.r[i] = dgrad_route(x6, p.packB[i], p.packXB[i], p.N, p.H, p.W, p.P.L[i], res_dgrad_nout(p, i));
   }
   B.head_x6 = x6 && p.C <= X6_HEAD_BWD_OCMAX;
   return B;
@@ -241,20 +211,16 @@ dn_status res_pack_forward(const ResPlan& p, const ResRoutes& R, const float* pr
   for (int i = R_ENC1; i <= R_D1B; ++i) {
     if (i == R_UP5) continue;
     const Layer& L = p.P.L[i];
-    const ResRoute& r = R.r[i];
+    const ConvRoute& r = R.r[i];
     const float* w = prm + L.woff;
     PackJob j;
-    if (r.kind == RK_X6)
+    if (r.kind == CV_X6)
       DN_TRY(add(pack_job_x6(conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 0, ws + r.img, r.tail, j), j));
     else
       DN_TRY(add(pack_job(G_C3, conv_fwd_view(w, L.cin, 3), L.cin, L.cout, 1, ws + r.img, 0, 0, j), j));
   }
-  const float* wa = prm + p.P.L[R_NINA].woff;
-  const float* wb = prm + p.P.L[R_NINB].woff;
-  if (R.head_x6)
-    DN_TRY(add(true, pack_job_head_x6(wa, wb, ws + p.packH)));
-  else
-    DN_TRY(launch_pack_head(conv_fwd_view(wa, 96, 1), conv_fwd_view(wb, 96, 1), ws + p.packH, s, &pb));
+  DN_TRY(pack_head_fwd(pb, R.head_x6, prm + p.P.L[R_NINA].woff, prm + p.P.L[R_NINB].woff,
+                       ws + p.packH, s));
   DN_TIMED(s, "pack", 0, 0, 0, 0, 0, 0, pack_flush(pb, s));
   return DN_OK;
 }
@@ -267,9 +233,9 @@ dn_status res_run_forward(const ResPlan& p, const ResRoutes& R, const float* prm
   // 3x3 conv layer i (bias + LeakyReLU) on the kernel and image of its route
   auto conv = [&](int i, const View& in, const View& out) -> hipError_t {
     const Layer& L = p.P.L[i];
-    const ResRoute& r = R.r[i];
+    const ConvRoute& r = R.r[i];
     const OpTimer timer(s, "fwd3", 2.0 * N * H * W * L.cin * L.cout * 9, L.cin, L.cout, H, W, N);
-    if (r.kind == RK_F32)
+    if (r.kind == CV_F32)
       return conv_forward(in, N, H, W, L.cin, ws + r.img, Bs(i), L.cout, 3, 1, out, OUT_NHWC, s);
     FwdArgs a = fwd_args(in, N, H, W, i == R_D1A ? p.c1kp : L.cin, L.cout, out, OUT_NHWC);
     a.wp = ws + r.img; a.bias = Bs(i); a.epi = EPI_BIAS_ACT;
@@ -295,16 +261,10 @@ dn_status res_run_forward(const ResPlan& p, const ResRoutes& R, const float* prm
   DN_TRY(conv(R_D1A, V(p.c1, p.c1s), V(p.d1a, 96)));
   DN_TRY(conv(R_D1B, V(p.d1a, 96), V(p.d1b, 96)));
   // nin_a -> nin_b -> nin_c + x in one launch
-  HeadArgs h{};
-  h.wp = ws + p.packH;
-  h.ba = Bs(R_NINA); h.bb = Bs(R_NINB);
-  h.wc = prm + p.P.L[R_NINC].woff; h.bc = Bs(R_NINC); h.oc = C;
-  h.y = y; h.res = x;
+  HeadArgs h = head_args(prm, p.P.L[R_NINA], p.P.L[R_NINB], p.P.L[R_NINC], ws + p.packH, y);
+  h.res = x;
   if (p.with_bwd) { h.na = ws + p.na; h.nb = ws + p.nb; }
-  const FwdArgs a = fwd_args(V(p.d1b, 96), N, H, W, 96, 96, View{nullptr, 0, 0}, OUT_NHWC);
-  DN_TIMED(s, "head", 2.0 * N * H * W * 96 * (2 * 96 + C), 96, C, H, W, N,
-           R.head_x6 ? launch_nin_head_x6(a, h, ws + p.packH, s) : launch_nin_head(a, h, s));
-  return DN_OK;
+  return head_forward(h, ws + p.d1b, N, H, W, R.head_x6, s);
 }
 
 }  // namespace
@@ -337,63 +297,28 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
   const ResRoutes B = res_bwd_routes(p, prec);
   {  // every data-gradient image, the head's, the zero padding: one launch
     PackBatch pb;
-    auto add = [&](bool ok, const PackJob& j) { return ok ? pack_add(pb, j, s) : hipErrorInvalidValue; };
-    for (int i = R_ENC1; i <= R_D1B; ++i) {
-      if (i == R_UP5) continue;
-      const Layer& L = p.P.L[i];
-      const ResRoute& r = B.r[i];
-      const float* w = prm + L.woff;
-      const int nout = res_dgrad_nout(p, i);
-      PackJob j;
-      if (r.kind == RK_X6)
-        DN_TRY(add(pack_job_x6(conv_dgrad_view(w, L.cin, 3), L.cout, nout, r.zc, ws + r.img, r.tail, j), j));
-      else
-        DN_TRY(add(pack_job(G_C3, conv_dgrad_view(w, L.cin, 3), L.cout, nout, 1, ws + r.img, 0, 0, j), j));
-    }
-    if (B.head_x6)
-      DN_TRY(add(true, pack_job_head_bwd_x6(prm + p.P.L[R_NINA].woff, prm + p.P.L[R_NINB].woff,
-                                            ws + p.packHB)));
-    else
-      DN_TRY(launch_pack_head(conv_dgrad_view(prm + p.P.L[R_NINB].woff, 96, 1),
-                              conv_dgrad_view(prm + p.P.L[R_NINA].woff, 96, 1), ws + p.packHB, s, &pb));
-    DN_TRY(add(true, pack_job_zero(ws + p.zeros, 64)));
+    for (int i = R_ENC1; i <= R_D1B; ++i)
+      if (i != R_UP5)
+        DN_TRY(pack_dgrad(pb, B.r[i], prm + p.P.L[i].woff, p.P.L[i], res_dgrad_nout(p, i), ws, s));
+    DN_TRY(pack_head_bwd(pb, B.head_x6, prm + p.P.L[R_NINA].woff, prm + p.P.L[R_NINB].woff,
+                         ws + p.packHB, ws + p.zeros, s));
     DN_TIMED(s, "pack", 0, 0, 0, 0, 0, 0, pack_flush(pb, s));
   }
-  RedBatch rb;
+  BwdStreams bs(s);
   const float* Z = ws + p.zeros;
-  SideStream* side = bwd_two_streams() && !prof_on() ? side_stream(s) : nullptr;
-  hipStream_t s2 = side ? side->st : s;
-  auto fork = [&] { return side_fork(side, s); };
-  auto flush_side = [&]() -> hipError_t {
-    if (!side) return red_flush(rb, s);
-    hipError_t e = hipEventRecord(side->rfork, s2);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->rst, side->rfork, 0);
-    if (e == hipSuccess) e = red_flush(rb, side->rst);
-    return e;
-  };
+  auto dst = [&](int i) { return WgradDst{G(i), SL(i), p.splits[i]}; };
+  const TailShape tail{N, H, W, x6, Z};
   // layer i: dz (its cout channels) -> dx = channels [0, res_dgrad_nout) of its input, * leaky'(mask)
   auto dgrad = [&](int i, const View& dz, const View& mask, const View& dxv) -> hipError_t {
-    const Layer& L = p.P.L[i];
-    const ResRoute& r = B.r[i];
-    const int nout = res_dgrad_nout(p, i);
-    const OpTimer timer(s, "dgrad3", 2.0 * N * H * W * L.cout * nout * 9, L.cout, nout, H, W, N);
-    if (r.kind == RK_F32)
-      return conv_dgrad(dz, N, H, W, L.cout, ws + r.img, nout, 3, EPI_MASK, mask, dxv, s);
-    FwdArgs a = fwd_args(dz, N, H, W, L.cout, nout, dxv, OUT_NHWC);
-    a.zc = r.zc;
-    a.wp = ws + r.img; a.wp_z = r.wp_z;
-    a.epi = EPI_MASK;
-    set_mask(a, mask);
-    a.x6_tail = r.tail;
-    return launch_fwd_x6(a, s);
+    return run_dgrad(B.r[i], ws, dz, N, H, W, p.P.L[i], res_dgrad_nout(p, i), EPI_MASK, mask, dxv, s);
   };
   // layer i's weight gradient on the side stream, behind the main stream's work so far
   auto wg = [&](int i, const View& g, const View& xv) -> hipError_t {
     const Layer& L = p.P.L[i];
-    hipError_t e = fork();
+    hipError_t e = bs.fork();
     if (e != hipSuccess) return e;
-    return wgrad(L.k == 3 ? W_C3 : W_C1, g, xv, N, H, W, L.cout, L.cin, G(i), SL(i), p.splits[i], s2,
-                 x6, Z, &rb);
+    return wgrad(L.k == 3 ? W_C3 : W_C1, g, xv, N, H, W, L.cout, L.cin, G(i), SL(i), p.splits[i], bs.s2,
+                 x6, Z, &bs.rb);
   };
 
   // dy arrives NCHW; out_nc == 1: that is NHWC
@@ -402,61 +327,22 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
     DN_TRY(launch_nchw_to_slice(dy, N, OC, H, W, ws + p.dyt, OC, 0, OC, s));
     dyv = V(p.dyt, OC);
   }
-  const bool head_gnb = B.head_x6;  // g_nb recomputed by nin_b's weight gradient (k_wgrad1p)
-  {
+  {  // nin_c .. nin_a: data gradients in one kernel, then the three 1x1 weight gradients
     HeadBwdArgs h{};
     h.wp = ws + p.packHB;
     h.wc = prm + p.P.L[R_NINC].woff; h.oc = OC;
     h.dy = dyv.p; h.dy_stride = dyv.stride;
     h.nb = ws + p.nb; h.na = ws + p.na; h.d1b = ws + p.d1b;
-    h.g_nb = head_gnb ? nullptr : ws + p.g_nb;
-    h.g_na = ws + p.g_na; h.g_d1b = ws + p.g_d1b;
+    h.g_nb = ws + p.g_nb; h.g_na = ws + p.g_na; h.g_d1b = ws + p.g_d1b;
     h.npx = px;
-    DN_TIMED(s, "head_bwd", 2.0 * px * 96 * (2 * 96 + OC), OC, 96, H, W, N,
-             B.head_x6 ? launch_head_bwd_x6(h, ws + p.packHB, s) : launch_head_bwd(h, s));
+    if (dn_status st = head_backward(bs, tail, h, B.head_x6, dst(R_NINA), dst(R_NINB), dst(R_NINC)))
+      return st;
   }
-  const bool fold_c = head_gnb && OC == 1;  // nin_c's weight gradient inside nin_b's
-  if (!fold_c) {
-    DN_TRY(fork());
-    DN_TIMED(s2, "wgrad1", 2.0 * px * 96 * OC, 96, OC, H, W, N,
-             launch_wgrad_thin(dyv.p, dyv.stride, OC, ws + p.nb, px, SL(R_NINC) + 64,
-                               p.splits[R_NINC], G(R_NINC), s2, &rb));
-  }
-  DN_TRY(fork());
-  const WgradHead hd{head_gnb ? OC : 0, dyv.p, dyv.stride, prm + p.P.L[R_NINC].woff,
-                     fold_c ? SL(R_NINC) + 64 : nullptr, G(R_NINC)};
-  DN_TRY(wgrad(W_C1, head_gnb ? V(p.nb, 96) : V(p.g_nb, 96), V(p.na, 96), N, H, W, 96, 96,
-               G(R_NINB), SL(R_NINB), p.splits[R_NINB], s2, x6, Z, &rb, &hd));
-  DN_TRY(wg(R_NINA, V(p.g_na, 96), V(p.d1b, 96)));
   DN_TRY(wg(R_D1B, V(p.g_d1b, 96), V(p.d1a, 96)));
   DN_TRY(dgrad(R_D1B, V(p.g_d1b, 96), V(p.d1a, 96), V(p.g_d1a, 96)));
-  // dec_conv1a's weight gradient: the MFMA kernel over [d2b] and the thin kernel over the
-  // network-input channels, each into its own slab rows (as the UNet's dec_conv1a)
-  {
-    const long n = (long)96 * p.c1k * 9 + 96;
-    float* slab = SL(R_D1A) + 64;
-    WgradArgs a{};
-    a.g = ws + p.g_d1a; a.g_stride = 96; a.g_off = 0;
-    a.x = ws + p.c1; a.x_stride = p.c1s; a.x_off = 0;
-    a.N = N; a.KH = H; a.KW = W; a.Cout = 96; a.Cin = 2 * nf;
-    a.zeros = Z; a.slab = slab; a.slab_stride = n;
-    a.wlayout = 0; a.cin_total = p.c1k; a.ci_base = 0; a.bias = 1;
-    const int sp = x6 ? wgrad_splits_x6(a, p.splits[R_D1A]) : p.splits[R_D1A];
-    DN_TRY(fork());
-    DN_TIMED(s2, "wgrad3", 2.0 * px * 96 * 2 * nf * 9, 2 * nf, 96, H, W, N,
-             launch_wgrad(W_C3, a, sp, s2, x6));
-    RedJob j = red_job(slab, n, sp, 96L * 2 * nf * 9, G(R_D1A));
-    j.ig = j.og = 2 * nf * 9;
-    j.is1 = j.os1 = p.c1k * 9;
-    DN_TRY(red_add(&rb, j, s2));
-    DN_TRY(red_add(&rb, red_job(slab + 96L * p.c1k * 9, n, sp, 96, G(R_D1A) + 96L * p.c1k * 9), s2));
-    float* thin = slab + (long)p.splits[R_D1A] * n;
-    const long nt = 96L * C * 9;
-    const int st = enc0_wgrad_splits(N, H, W);
-    DN_TIMED(s2, "wgrad3_thin", 2.0 * px * 96 * C * 9, C, 96, H, W, N,
-             launch_wgrad_c3_thin(ws + p.g_d1a, 96, ws + p.xin, N, C, H, W, thin, nt, C, 0, 0, st, s2));
-    DN_TRY(launch_reduce_scatter(thin, nt, st, nt, G(R_D1A), 9L * C, 9L * p.c1k, 9L * 2 * nf, s2, &rb));
-  }
+  // dec_conv1a's weight gradient: [d2b]'s channels and the network input's (as the UNet's)
+  if (dn_status st = d1a_wgrad(bs, tail, ws + p.g_d1a, V(p.c1, p.c1s), p.c1k, ws + p.xin, C, dst(R_D1A)))
+    return st;
   // [d2b]'s gradient; the image channels of c1 carry no activation and get theirs in dgrad_input
   DN_TRY(dgrad(R_D1A, V(p.g_d1a, 96), V(p.c1, p.c1s, 0), V(p.g_c1, 2 * nf)));
   View g = V(p.g_c1, 2 * nf);  // pre-activation gradient of dec_conv{k}b's output
@@ -469,7 +355,7 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
     DN_TRY(dgrad(ia, V(p.g_da[k], 2 * nf), V(p.c[k], p.cs[k]), V(p.g_c[k], p.cs[k])));
     g = V(p.g_c[k], p.cs[k], 0);
   }
-  if (side) DN_TIMED(side->rst, "reduce", 0, 0, 0, 0, 0, 0, flush_side());
+  DN_TRY(bs.flush_reductions());
   // enc_conv6 (input a5), then enc_conv5 .. enc_conv2 (input a_j = the skip slice of c_{j+1})
   DN_TRY(wg(R_ENC6, V(p.g_c[5], p.cs[5], 0), V(p.a5, nf)));
   DN_TRY(dgrad(R_ENC6, V(p.g_c[5], p.cs[5], 0), V(p.a5, nf), V(p.g_a5, nf)));
@@ -483,24 +369,19 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
              launch_add_slice(ws + p.g_c[k], p.cs[k], so, ws + p.g_t, nf, px, ws + p.g_a[j], s));
     ge = V(p.g_a[j], nf);
   }
-  if (side) DN_TIMED(side->rst, "reduce", 0, 0, 0, 0, 0, 0, flush_side());
+  DN_TRY(bs.flush_reductions());
   // enc_conv1 (input a0), enc_conv0 (input x)
   DN_TRY(dgrad(R_ENC1, ge, V(p.a0, nf), V(p.g_a0, nf)));
-  DN_TRY(fork());
-  DN_TIMED(s2, "wgrad3_thin", 2.0 * px * nf * C * 9, C, nf, H, W, N,
+  DN_TRY(bs.fork());
+  DN_TIMED(bs.s2, "wgrad3_thin", 2.0 * px * nf * C * 9, C, nf, H, W, N,
            launch_enc0_wgrad(ws + p.g_a0, nf, ws + p.xin, N, C, H, W, SL(R_ENC0) + 64,
-                             p.splits[R_ENC0], G(R_ENC0), s2, &rb));
+                             p.splits[R_ENC0], G(R_ENC0), bs.s2, &bs.rb));
   DN_TRY(wgrad(W_C3, ge, V(p.a0, nf), N, H, W, nf, nf, G(R_ENC1), SL(R_ENC1), p.splits[R_ENC1], s,
-               x6, Z, &rb));
+               x6, Z, &bs.rb));
   // up5.deconv is never used: an exact zero gradient (dparams is overwritten, not accumulated)
   DN_TRY(hipMemsetAsync(G(R_UP5), 0, (p.P.L[R_UP5].wcount + p.P.L[R_UP5].cout) * sizeof(float), s));
-  if (side) {
-    DN_TRY(hipEventRecord(side->join, s2));
-    DN_TRY(hipStreamWaitEvent(s, side->join, 0));
-    DN_TRY(hipEventRecord(side->rjoin, side->rst));
-    DN_TRY(hipStreamWaitEvent(s, side->rjoin, 0));
-  }
-  DN_TIMED(s, "reduce", 0, 0, 0, 0, 0, 0, red_flush(rb, s));
+  DN_TRY(bs.join());
+  DN_TIMED(s, "reduce", 0, 0, 0, 0, 0, 0, red_flush(bs.rb, s));
   // dL/dx = dy + enc_conv0^T g_a0 + (image-channel slice of dec_conv1a's data gradient)
   if (dx)
     DN_TIMED(s, "dgrad_input", 0, 0, 0, 0, 0, 0,

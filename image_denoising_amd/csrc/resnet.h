@@ -1,10 +1,10 @@
 // Host-side RESNET plan and orchestration (internal): arch_unet.py:263-409, the UNet's layers
 // without pooling or upsampling (every layer at the input resolution) and the network input added
-// to nin_c's output.  Shares the UNet's kernels, views and helpers (unet.h).
+// to nin_c's output.  Shares the UNet's kernels, views and helpers (exec_common.h).
 #pragma once
 #include <string>
 
-#include "unet.h"
+#include "exec_common.h"
 
 namespace dn {
 

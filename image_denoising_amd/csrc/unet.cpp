@@ -1,21 +1,13 @@
 // U-Net orchestration for the N2N training path: parameter layout (reference state_dict
 // order), workspace plan (NHWC activation arena, gradient buffers, weight-gradient slabs),
 // and the forward / backward launch sequences.  Mirrors arch_unet.py:100-260 (UNet) and
-// the autograd graph that `loss.backward()` replays for it.
+// the autograd graph that `loss.backward()` replays for it.  The op helpers, the backward's
+// streams and the dec_conv1a .. nin_c tail shared with resnet.cpp live in exec_common.{h,cpp}.
 #include "unet.h"
 
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
 
 namespace dn {
-
-thread_local std::string g_last_error;
-
-void set_error(const std::string& s) { g_last_error = s; }
 
 // ------------------------------------------------------------------------------------
 // parameters: arch_unet.py:115-192 registration order (== state_dict order)
@@ -230,29 +222,19 @@ bool build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, Plan& p, st
       int KH = H >> lvl, KW = W >> lvl;
       int mode = L.deconv ? W_UP2 : (L.k == 3 ? W_C3 : W_C1);
       if (L.deconv) { KH = H >> (lvl + 1); KW = W >> (lvl + 1); }
-      int sp = i == ENC0   ? enc0_wgrad_splits(N, KH, KW)
-               : (i == NINC && p.OC <= 4) ? wgrad_thin_splits((long)N * KH * KW)
-                           : wgrad_splits(mode, N, KH, KW, i == D1A ? 2 * nf : L.cin, L.cout);
-      p.splits[i] = sp;
-      long need = (i == ENC0 || i == D1A || (i == NINC && p.OC <= 4))
-                      ? (long)sp * (L.wcount + L.cout)
-                      : wgrad_slab_floats(mode, N, KH, KW, L.cin, L.cout);
-      // (nin_c: also the rows nin_b's k_wgrad1p<., GNB> writes its weight gradient into)
-      if (i == NINC && p.OC <= 4) {
-        const long s1 = wgrad1_splits(W_C1, N, KH, KW);
-        if (s1 * (L.wcount + L.cout) > need) need = s1 * (L.wcount + L.cout);
-      }
-      if (i == D1A) need += (long)enc0_wgrad_splits(N, KH, KW) * 96 * p.C * 9;  // input slice
-      p.slab[i] = alloc_f(64 + need);
-      p.slab_floats += 64 + need;
+      // (nin_c above 4 outputs goes through wgrad() like any 1x1 layer)
+      const int kind = i == ENC0 ? SLAB_ENC0 : i == D1A ? SLAB_D1A
+                       : (i == NINC && p.OC <= 4) ? SLAB_NINC_THIN : SLAB_CONV;
+      const WgradSlab sl = plan_wgrad_slab(kind, mode, N, KH, KW, L, p.C);
+      p.splits[i] = sl.splits;
+      p.slab[i] = alloc_f(64 + sl.floats);
+      p.slab_floats += 64 + sl.floats;
     }
   }
   p.total_floats = off;
   p.with_bwd = bwd;
   return true;
 }
-
-int x6_dgrad_zc(int nout) { return nout <= 96 ? 0 : 48; }
 
 // channels of the data gradient a layer's backward must produce
 int dgrad_nout(const Plan& p, int i) {
@@ -275,123 +257,6 @@ int layer_level(int i) {
     case UP2: case D2A: case D2B: return 1;
     default: return 0;  // UP1, D1A, D1B, NIN*
   }
-}
-
-// ------------------------------------------------------------------------------------
-// op helpers
-// ------------------------------------------------------------------------------------
-#define DN_TRY(x)                                                         \
-  do {                                                                    \
-    hipError_t e_ = (x);                                                  \
-    if (e_ != hipSuccess) {                                               \
-      set_error(std::string("HIP error in ") + #x + ": " + hipGetErrorString(e_)); \
-      return DN_ERR_HIP;                                                  \
-    }                                                                     \
-  } while (0)
-
-WView conv_fwd_view(const float* w, int K, int ksize) {
-  return ksize == 3 ? WView{w, 0, 9, (long)K * 9, 1, 0, 9, 0} : WView{w, 0, 1, (long)K, 0, 0, 1, 0};
-}
-WView conv_dgrad_view(const float* w, int cin_total, int ksize) {  // flipped + transposed
-  return ksize == 3 ? WView{w, 0, (long)cin_total * 9, 9, 1, 0, 9, 1}
-                    : WView{w, 0, (long)cin_total, 1, 0, 0, 1, 0};
-}
-WView deconv_fwd_view(const float* w, int cout) { return WView{w, 0, (long)cout * 4, 4, 0, 1, 1, 0}; }
-WView deconv_dgrad_view(const float* w, int cout) { return WView{w, 0, 4, (long)cout * 4, 1, 0, 4, 0}; }
-
-long conv_fwd_pack_size(int K, int cout, int ksize) {
-  return pack_floats(ksize == 3 ? G_C3 : G_C1, cout, K, 1);
-}
-long conv_dgrad_pack_size(int cout, int nout, int ksize) {
-  return pack_floats(ksize == 3 ? G_C3 : G_C1, nout, cout, 1);
-}
-long deconv_fwd_pack_size(int cin, int cout) { return pack_floats(G_UP, cout, cin, 4); }
-long deconv_dgrad_pack_size(int cout, int cin) { return pack_floats(G_DN2, cin, cout, 1); }
-
-hipError_t pack_conv_fwd(const float* w, int K, int cout, int ksize, float* out, hipStream_t s) {
-  return launch_pack(ksize == 3 ? G_C3 : G_C1, conv_fwd_view(w, K, ksize), K, cout, 1, out, s);
-}
-hipError_t pack_conv_dgrad(const float* w, int cin_total, int nout, int cout, int ksize, float* out,
-                           hipStream_t s) {
-  return launch_pack(ksize == 3 ? G_C3 : G_C1, conv_dgrad_view(w, cin_total, ksize), cout, nout, 1,
-                     out, s);
-}
-hipError_t pack_deconv_fwd(const float* w, int cin, int cout, float* out, hipStream_t s) {
-  return launch_pack(G_UP, deconv_fwd_view(w, cout), cin, cout, 4, out, s);
-}
-hipError_t pack_deconv_dgrad(const float* w, int cout, int cin, float* out, hipStream_t s) {
-  return launch_pack(G_DN2, deconv_dgrad_view(w, cout), cout, cin, 1, out, s);
-}
-
-hipError_t conv_forward(const View& in, int N, int H, int W, int K, const float* wp,
-                        const float* b, int cout, int ksize, int act, const View& out,
-                        int out_layout, hipStream_t s) {
-  FwdArgs a = fwd_args(in, N, H, W, K, cout, out, out_layout);
-  a.wp = wp;
-  a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
-  return launch_fwd(ksize == 3 ? G_C3 : G_C1, a, s);
-}
-
-// dx (channels [0, nout)) from dz [N,H,W,cout]; wp = pack_conv_dgrad(...)
-hipError_t conv_dgrad(const View& dz, int N, int H, int W, int cout, const float* wp, int nout,
-                      int ksize, int epi, const View& mask, const View& dx, hipStream_t s) {
-  FwdArgs a = fwd_args(dz, N, H, W, cout, nout, dx, OUT_NHWC);
-  a.wp = wp;
-  a.epi = epi;
-  set_mask(a, mask);
-  return launch_fwd(ksize == 3 ? G_C3 : G_C1, a, s);
-}
-
-// ConvTranspose2d(cin, cout, 2, 2): x [N,h,w,cin] -> out at (2y+a, 2x+b); wp = pack_deconv_fwd
-hipError_t deconv_forward(const View& x, int N, int h, int w, int cin, const float* wp,
-                          const float* b, int cout, const View& out, hipStream_t s) {
-  FwdArgs a = fwd_args(x, N, h, w, cin, cout, out, OUT_UP2);
-  a.wp = wp; a.wp_z = pack_floats(G_UP, cout, cin, 1);
-  a.bias = b; a.epi = EPI_BIAS;
-  return launch_fwd(G_UP, a, s);
-}
-
-// dx [N,h,w,cin] = sum_{ab,co} dy[2y+a][2x+b][co] * W[ci][co][ab]  (* leaky'(mask));
-// wp = pack_deconv_dgrad
-hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const float* wp, int cin,
-                        const View& mask, int epi, const View& dx, hipStream_t s) {
-  FwdArgs a = fwd_args(dy, 2 * h, 2 * w, N, h, w, cout, cin, dx, OUT_NHWC);
-  a.wp = wp;
-  a.epi = epi;
-  set_mask(a, mask);
-  return launch_fwd(G_DN2, a, s);
-}
-
-hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
-                 float* dwb, float* slab, int splits, hipStream_t s, bool x6, const float* zeros,
-                 RedBatch* rb, const WgradHead* head) {
-  WgradArgs a{};
-  if (head) {
-    a.head_gnb = head->gnb; a.hd_dy = head->dy; a.hd_dy_stride = head->dy_stride;
-    a.hd_wc = head->wc; a.hd_slab_c = head->slab_c; a.hd_dwc = head->dwc;
-  }
-  a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
-  a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
-  a.N = N; a.KH = KH; a.KW = KW; a.Cout = cout; a.Cin = cin;
-  const int taps = mode == W_C3 ? 9 : (mode == W_UP2 ? 4 : 1);
-  const long n = (long)cout * cin * taps + cout;
-  const OpTimer timer(s, mode == W_C3 ? "wgrad3" : (mode == W_UP2 ? "wgrad_up" : "wgrad1"),
-                      2.0 * N * KH * KW * cout * cin * taps, cin, cout, KH, KW, N);
-  // slab scratch layout: [64 floats | splits x (W + b)]
-  a.zeros = zeros ? zeros : slab;
-  a.slab = slab + 64; a.slab_stride = n;
-  a.wlayout = mode == W_UP2 ? 1 : 0;
-  a.cin_total = cin; a.ci_base = 0; a.bias = 1;
-  if (!zeros) {
-    hipError_t e = hipMemsetAsync(slab, 0, 64 * sizeof(float), s);
-    if (e != hipSuccess) return e;
-  }
-  // 1x1 / deconv, own splits (x6: the 96 x 96 1x1 layers on k_wgrad1p)
-  if (wgrad1_ok(mode, a)) return launch_wgrad1(mode, a, dwb, s, rb, x6);
-  if (x6 && mode == W_C3) splits = wgrad_splits_x6(a, splits);
-  hipError_t e = launch_wgrad(mode, a, splits, s, x6);
-  if (e != hipSuccess) return e;
-  return launch_reduce(slab + 64, n, splits, n, dwb, s, rb);
 }
 
 // ------------------------------------------------------------------------------------
@@ -576,18 +441,9 @@ dn_status pack_forward(const Plan& p, const FwdRoutes& R, const float* prm, floa
       DN_TRY(add(pack_job_x6(v, L.cin, L.cout, 0, ws + R.img_xv, X6_W6, j), j));
     }
   }
-  const float* wa = prm + p.P.L[NINA].woff;
-  const float* wb = prm + p.P.L[NINB].woff;
-  switch (R.head) {
-    case H_NIN_X6: case H_NIN_BF16:
-      DN_TRY(add(true, pack_job_head_x6(wa, wb, ws + R.head_img)));
-      break;
-    case H_F32: case H_NIN:
-      DN_TRY(launch_pack_head(conv_fwd_view(wa, 96, 1), conv_fwd_view(wb, 96, 1), ws + R.head_img, s, &pb));
-      break;
-    case H_BF16_3:  // the three layers' own images, above
-      break;
-  }
+  if (R.head != H_BF16_3)  // (H_BF16_3: the three layers' own images, above)
+    DN_TRY(pack_head_fwd(pb, R.head == H_NIN_X6 || R.head == H_NIN_BF16, prm + p.P.L[NINA].woff,
+                         prm + p.P.L[NINB].woff, ws + R.head_img, s));
   DN_TIMED(s, "pack", 0, 0, 0, 0, 0, 0, pack_flush(pb, s));
   return DN_OK;
 }
@@ -707,16 +563,9 @@ dn_status run_forward(const Plan& p, const FwdRoutes& R, const float* prm, const
   // reads den at the pair pixels only) runs both on those pixels, through the [N, H/2, W, 96] pair
   // image in d1b's storage
   const int hh = R.sel ? H(0) / 2 : H(0);  // rows of the head's input
-  HeadArgs h{};
-  h.wp = ws + R.head_img;
-  h.ba = Bs(NINA); h.bb = Bs(NINB);
-  h.wc = prm + p.P.L[NINC].woff; h.bc = Bs(NINC); h.oc = p.OC;
-  h.y = y;
+  HeadArgs h = head_args(prm, p.P.L[NINA], p.P.L[NINB], p.P.L[NINC], ws + R.head_img, y);
   // the intermediate activations are written only when a backward will read them
   if (p.with_bwd) { h.na = ws + p.na; h.nb = ws + p.nb; }
-  // the head kernels' input: the activated dec_conv1b output, 96 -> 96
-  FwdArgs a = fwd_args(V(p.d1b, 96), N, hh, Wd(0), 96, 96, none, OUT_NHWC);
-  const double head_flops = 2.0 * N * hh * Wd(0) * 96 * (2 * 96 + p.OC);
   // dec_conv1b where it is not conv_forward's: the pair pass, the fp32 head kernel
   FwdArgs ac = fwd_args(V(p.d1a, 96), N, H(0), Wd(0), 96, 96, V(p.d1b, 96), OUT_NHWC);
   ac.wp = ws + R.r[D1B].img; ac.bias = Bs(D1B); ac.epi = EPI_BIAS_ACT;
@@ -739,18 +588,16 @@ dn_status run_forward(const Plan& p, const FwdRoutes& R, const float* prm, const
       DN_TIMED(s, "fwd3+head", 2.0 * N * H(0) * Wd(0) * 96 * (9 * 96 + 2 * 96 + p.OC), 96, 96, H(0),
                Wd(0), N, launch_head(ac, h, s));
       break;
-    case H_NIN:
-      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N, launch_nin_head(a, h, s));
+    case H_NIN: case H_NIN_X6:
+      if (dn_status st = head_forward(h, ws + p.d1b, N, hh, Wd(0), R.head == H_NIN_X6, s)) return st;
       break;
-    case H_NIN_X6:
-      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N,
-               launch_nin_head_x6(a, h, ws + R.head_img, s));
-      break;
-    case H_NIN_BF16:
-      a.in_bf16 = R.r[D1B].out_bf16;  // d1b stored as bf16 by dec_conv1b
-      DN_TIMED(s, "head", head_flops, 96, p.OC, hh, Wd(0), N,
+    case H_NIN_BF16: {  // the head kernels' input: d1b, stored as bf16 by dec_conv1b
+      FwdArgs a = fwd_args(V(p.d1b, 96), N, hh, Wd(0), 96, 96, none, OUT_NHWC);
+      a.in_bf16 = R.r[D1B].out_bf16;
+      DN_TIMED(s, "head", 2.0 * N * hh * Wd(0) * 96 * (2 * 96 + p.OC), 96, p.OC, hh, Wd(0), N,
                launch_nin_head_x6(a, h, ws + R.head_img, s, /*bf16=*/true));
       break;
+    }
     case H_BF16_3: {
       DN_TRY(conv_forward(NINA, V(p.d1b, 96), V(p.na, 96)));
       DN_TRY(conv_forward(NINB, V(p.na, 96), V(p.nb, 96)));
@@ -782,83 +629,16 @@ dn_status unet_forward(const Plan& p, const float* prm, const float* x, float* y
 // LeakyReLU' into their epilogue (mask = the layer input, which is the previous layer's
 // post-activation output); skip gradients are accumulated into the concat-gradient buffers.
 // ------------------------------------------------------------------------------------
-// The weight gradients of the backward run on a second stream (DN_BWD_STREAMS=0: one stream):
-// they only read gradients and forward activations that nothing later in the backward rewrites
-// (the accumulations into a concat gradient's skip slice touch channels no weight gradient
-// reads) and write their own slabs, so they overlap the data-gradient chain; each is forked
-// from the main stream after the kernel that produced its gradient, and the branch is joined
-// before the batched reduction.  (struct SideStream: unet.h)
-//
-// One side stream (and its fork / join events) per host thread and device: keyed on the
-// device of the caller's stream (not hipGetDevice(), which a caller need not have set to it) and
-// created under a guard for that device; thread-local, so two host threads running backwards on
-// one device never share the events between a record and its wait.  The owner destroys them when
-// its thread exits (executors called from short-lived threads do not leak streams).
-struct SideStreams {
-  std::map<int, SideStream> per_device;
-  ~SideStreams() {
-    for (auto& kv : per_device) {
-      SideStream& ss = kv.second;
-      if (!ss.st) continue;
-      // (HIP releases a stream / event with work still pending once that work completes)
-      (void)hipEventDestroy(ss.fork);
-      (void)hipEventDestroy(ss.join);
-      (void)hipEventDestroy(ss.rfork);
-      (void)hipEventDestroy(ss.rjoin);
-      (void)hipStreamDestroy(ss.st);
-      (void)hipStreamDestroy(ss.rst);
-    }
-  }
-};
-
-SideStream* side_stream(hipStream_t s) {
-  thread_local SideStreams owner;
-  std::map<int, SideStream>& per_device = owner.per_device;
-  hipDevice_t dev = 0;
-  if (hipStreamGetDevice(s, &dev) != hipSuccess) return nullptr;
-  SideStream& ss = per_device[dev];
-  if (!ss.st) {
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return nullptr;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
-    if (hipStreamCreateWithFlags(&ss.st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ss.join, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&ss.rst, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ss.rfork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ss.rjoin, hipEventDisableTiming) != hipSuccess)
-      ss = SideStream{};
-    if (cur != dev) (void)hipSetDevice(cur);
-    if (!ss.st) return nullptr;
-  }
-  return &ss;
-}
-
-bool bwd_two_streams() {
-  static const bool on = !getenv("DN_BWD_STREAMS") || atoi(getenv("DN_BWD_STREAMS")) != 0;
-  return on;
-}
-
-hipError_t side_fork(SideStream* side, hipStream_t s) {
-  if (!side) return hipSuccess;
-  hipError_t e = hipEventRecord(side->fork, s);
-  return e != hipSuccess ? e : hipStreamWaitEvent(side->st, side->fork, 0);
-}
-
+// Weight gradients and slab reductions on their own streams: BwdStreams (exec_common.h).
 long tail_begin(const Plan& p) { return p.P.L[D5A].woff; }
 
 // The data-gradient route of every layer (enc_conv1 .. dec_conv1b), decided once: the pack loop
-// writes the image the launch reads
+// writes the image the launch reads.  Convs: dgrad_route (CV_F32: Plan::packB, CV_X6: packXB)
 namespace {
-enum BwdKind {
-  B_F32,     // conv data gradient on the fp32 kernel (Plan::packB)
-  B_X6,      // 3x3 on the bf16x6 kernels (packXB: zc-blocked image, tail as in the forward)
-  B_UP_F32,  // deconv data gradient on the fp32 kernel
-  B_UP_X6,   // ... of the 96-channel deconvs in the bf16x6 arithmetic (packUXB)
-};
-struct BwdRoute { int kind; long img; int zc; long wp_z; int tail; };
+// deconv data gradient on the fp32 kernel | of the 96-channel deconvs in bf16x6 (packUXB)
+enum BwdKind { B_UP_F32 = CV_END, B_UP_X6 };
 struct BwdRoutes {
-  BwdRoute r[NL];
+  ConvRoute r[NL];
   bool head_x6;  // the head's data gradients in the bf16x6 arithmetic (k_head_bwd_x6)
 };
 BwdRoutes bwd_routes(const Plan& p, int prec) {
@@ -866,19 +646,11 @@ BwdRoutes bwd_routes(const Plan& p, int prec) {
   BwdRoutes B{};
   for (int i = ENC1; i < NINA; ++i) {
     const Layer& L = p.P.L[i];
-    BwdRoute& r = B.r[i];
-    if (L.deconv) {
-      r.kind = x6 && p.packUXB[i] >= 0 ? B_UP_X6 : B_UP_F32;
-      r.img = r.kind == B_UP_X6 ? p.packUXB[i] : p.packB[i];
-    } else if (x6 && p.packXB[i] >= 0) {
-      const int l = layer_level(i), nout = dgrad_nout(p, i);
-      r.kind = B_X6; r.img = p.packXB[i];
-      r.zc = x6_dgrad_zc(nout);
-      r.wp_z = x6_wp_z(L.cout, nout, r.zc);
-      r.tail = x6_image_mode(p.N, p.H >> l, p.W >> l, L.cout, nout, r.zc, true);
-    } else {
-      r.kind = B_F32; r.img = p.packB[i];
-    }
+    const int l = layer_level(i);
+    if (L.deconv)
+      B.r[i] = x6 && p.packUXB[i] >= 0 ? ConvRoute{B_UP_X6, p.packUXB[i]} : ConvRoute{B_UP_F32, p.packB[i]};
+    else
+      B.r[i] = dgrad_route(x6, p.packB[i], p.packXB[i], p.N, p.H >> l, p.W >> l, L, dgrad_nout(p, i));
   }
   B.head_x6 = x6 && p.OC <= X6_HEAD_BWD_OCMAX;
   return B;
@@ -889,8 +661,6 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
                         float* ws, hipStream_t s, int prec, hipEvent_t tail_ready) {
   const StreamDeviceGuard device_guard(s);
   const bool x6 = prec == DN_PREC_FP32_X6;
-  // bf16x6 3x3 weight gradients (k_wgrad3p / k_wgrad3q)
-  const bool x6w = x6;
   const int N = p.N, nf = p.nf, C = p.C;
   auto H = [&](int l) { return p.H >> l; };
   auto Wd = [&](int l) { return p.W >> l; };
@@ -901,7 +671,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   auto deconv_dgrad = [&](int i, const View& dy, const View& mask, int epi, const View& dx,
                           hipStream_t st) -> hipError_t {
     const Layer& L = p.P.L[i];
-    const BwdRoute& r = B.r[i];
+    const ConvRoute& r = B.r[i];
     const int l = layer_level(i) + 1, h = H(l), w = Wd(l);
     const OpTimer timer(st, "deconv_dgrad", 2.0 * N * h * w * L.cin * L.cout * 4, L.cout, L.cin, h,
                         w, N);
@@ -912,162 +682,67 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     set_mask(a, mask);
     return launch_deconv_dgrad_x6(a, ws + r.img, st);
   };
-  const bool head_bwd_x6 = B.head_x6;
-  // g_nb (the nin_b output's gradient) recomputed by nin_b's weight gradient (k_wgrad1p<., GNB>)
-  // from nb and dy instead of being stored by k_head_bwd_x6 and read back (384 B per pixel less)
-  const bool head_gnb = head_bwd_x6;
-  // flipped/transposed weight images for the data gradients, the head's images and the
-  // weight gradients' zero padding: one launch
-  {
+  {  // the data gradients' flipped / transposed images, the head's, the zero padding: one launch
     PackBatch pb;
-    auto add = [&](bool ok, const PackJob& j) { return ok ? pack_add(pb, j, s) : hipErrorInvalidValue; };
     for (int i = ENC1; i < NINA; ++i) {
       const Layer& L = p.P.L[i];
-      const BwdRoute& r = B.r[i];
+      const ConvRoute& r = B.r[i];
       const float* w = prm + L.woff;
       PackJob j;
       switch (r.kind) {
         case B_UP_X6:
-          DN_TRY(add(true, pack_job_deconv_dgrad_x6(w, ws + r.img)));
+          DN_TRY(pack_add(pb, pack_job_deconv_dgrad_x6(w, ws + r.img), s));
           break;
         case B_UP_F32:
-          DN_TRY(add(pack_job(G_DN2, deconv_dgrad_view(w, L.cout), L.cout, L.cin, 1, ws + r.img, 0, 0, j), j));
+          DN_TRY(pack_job(G_DN2, deconv_dgrad_view(w, L.cout), L.cout, L.cin, 1, ws + r.img, 0, 0, j)
+                     ? pack_add(pb, j, s) : hipErrorInvalidValue);
           break;
-        case B_X6:
-          DN_TRY(add(pack_job_x6(conv_dgrad_view(w, L.cin, 3), L.cout, dgrad_nout(p, i), r.zc,
-                                 ws + r.img, r.tail, j), j));
-          break;
-        case B_F32:
-          DN_TRY(add(pack_job(L.k == 3 ? G_C3 : G_C1, conv_dgrad_view(w, L.cin, L.k), L.cout,
-                              dgrad_nout(p, i), 1, ws + r.img, 0, 0, j), j));
+        default:
+          DN_TRY(pack_dgrad(pb, r, w, L, dgrad_nout(p, i), ws, s));
           break;
       }
     }
-    if (head_bwd_x6)
-      DN_TRY(add(true, pack_job_head_bwd_x6(prm + p.P.L[NINA].woff, prm + p.P.L[NINB].woff, ws + p.packHB)));
-    else
-      DN_TRY(launch_pack_head(conv_dgrad_view(prm + p.P.L[NINB].woff, 96, 1),
-                              conv_dgrad_view(prm + p.P.L[NINA].woff, 96, 1), ws + p.packHB, s, &pb));
-    DN_TRY(add(true, pack_job_zero(ws + p.zeros, 64)));
+    DN_TRY(pack_head_bwd(pb, B.head_x6, prm + p.P.L[NINA].woff, prm + p.P.L[NINB].woff,
+                         ws + p.packHB, ws + p.zeros, s));
     DN_TIMED(s, "pack", 0, 0, 0, 0, 0, 0, pack_flush(pb, s));
   }
-  RedBatch rb;  // every weight gradient's reduction, launched together at the end
+  BwdStreams bs(s);
   const float* Z = ws + p.zeros;
-  // (profiling: one stream, so each launch's event pair brackets that kernel alone)
-  SideStream* side = bwd_two_streams() && !prof_on() ? side_stream(s) : nullptr;
-  hipStream_t s2 = side ? side->st : s;
-  auto fork = [&] { return side_fork(side, s); };
-  // the queued slab reductions on the reduction stream, behind the weight gradients queued on
-  // the side stream so far (one stream: on s, in order)
-  auto flush_side = [&]() -> hipError_t {
-    if (!side) return red_flush(rb, s);
-    hipError_t e = hipEventRecord(side->rfork, s2);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->rst, side->rfork, 0);
-    if (e == hipSuccess) e = red_flush(rb, side->rst);
-    return e;
-  };
   auto SL = [&](int i) { return ws + p.slab[i]; };
-  // 3x3 data gradients: the fp32 kernel or the bf16x6 one
+  auto dst = [&](int i) { return WgradDst{G(i), SL(i), p.splits[i]}; };
   // layer i: dz (the layer's cout channels) -> dx, channels [0, dgrad_nout(p, i)) of its input
   auto conv_dgrad = [&](int i, const View& dz, int epi, const View& mask, const View& dx,
                         hipStream_t st) -> hipError_t {
-    const Layer& L = p.P.L[i];
-    const BwdRoute& r = B.r[i];
-    const int l = layer_level(i), h = H(l), w = Wd(l), cout = L.cout, nout = dgrad_nout(p, i);
-    const OpTimer timer(st, L.k == 3 ? "dgrad3" : "dgrad1",
-                        2.0 * N * h * w * cout * nout * L.k * L.k, cout, nout, h, w, N);
-    if (r.kind == B_F32)
-      return dn::conv_dgrad(dz, N, h, w, cout, ws + r.img, nout, L.k, epi, mask, dx, st);
-    FwdArgs a = fwd_args(dz, N, h, w, cout, nout, dx, OUT_NHWC);
-    a.zc = r.zc;
-    a.wp = ws + r.img; a.wp_z = r.wp_z;
-    a.epi = epi;
-    set_mask(a, mask);
-    a.x6_tail = r.tail;
-    return launch_fwd_x6(a, st);
+    const int l = layer_level(i);
+    return run_dgrad(B.r[i], ws, dz, N, H(l), Wd(l), p.P.L[i], dgrad_nout(p, i), epi, mask, dx, st);
   };
   const View none{nullptr, 0, 0};
   const int OC = p.OC;
+  const TailShape tail{N, H(0), Wd(0), x6, Z};
 
-  // dy arrives NCHW [N, OC, H, W]; for OC == 1 that equals NHWC.  For OC > 1 transpose
-  // into g_c1's storage first (free at this point).
+  // dy arrives NCHW; OC == 1: that is NHWC.  OC > 1: transposed into g_c1's storage (free here)
   View dyv{const_cast<float*>(dy), OC, 0};
   if (OC > 1) {
     DN_TRY(launch_nchw_to_slice(dy, N, OC, p.H, p.W, ws + p.g_c1, OC, 0, OC, s));
     dyv = V(p.g_c1, OC);
   }
-  // nin_c -> nin_b -> nin_a data gradients in one kernel (g_nb, g_na, g_d1b), then the three
-  // 1x1 weight gradients from them
-  {
+  {  // nin_c .. nin_a: data gradients in one kernel, then the three 1x1 weight gradients
     HeadBwdArgs h{};
     h.wp = ws + p.packHB;
     h.wc = prm + p.P.L[NINC].woff; h.oc = OC;
     h.dy = dyv.p; h.dy_stride = dyv.stride;
     h.nb = ws + p.nb; h.na = ws + p.na; h.d1b = ws + p.d1b;
-    // (head_gnb: nin_b's weight gradient recomputes g_nb, nothing reads a stored one)
-    h.g_nb = head_gnb ? nullptr : ws + p.g_nb;
-    h.g_na = ws + p.g_na; h.g_d1b = ws + p.g_d1b;
+    h.g_nb = ws + p.g_nb; h.g_na = ws + p.g_na; h.g_d1b = ws + p.g_d1b;
     h.npx = (long)N * H(0) * Wd(0);
-    DN_TIMED(s, "head_bwd", 2.0 * h.npx * 96 * (2 * 96 + OC), OC, 96, H(0), Wd(0), N,
-             head_bwd_x6 ? launch_head_bwd_x6(h, ws + p.packHB, s) : launch_head_bwd(h, s));
+    if (dn_status st = head_backward(bs, tail, h, B.head_x6, dst(NINA), dst(NINB), dst(NINC))) return st;
   }
-  const bool fold_c = head_gnb && OC == 1;  // nin_c's weight gradient inside nin_b's (k_wgrad1p)
-  if (!fold_c) {
-    DN_TRY(fork());
-    if (OC <= 4)
-      DN_TIMED(s2, "wgrad1", 2.0 * N * H(0) * Wd(0) * 96 * OC, 96, OC, H(0), Wd(0), N,
-               launch_wgrad_thin(dyv.p, dyv.stride, OC, ws + p.nb, (long)N * H(0) * Wd(0),
-                               SL(NINC) + 64, p.splits[NINC], G(NINC), s2, &rb));
-    else
-      DN_TRY(wgrad(W_C1, dyv, V(p.nb, 96), N, H(0), Wd(0), OC, 96, G(NINC), SL(NINC),
-                   p.splits[NINC], s2, false, Z, &rb));
-  }
-  DN_TRY(fork());
-  // (head_gnb: the gradient operand g_nb recomputed from nb and dy inside k_wgrad1p, which also
-  // forms nin_c's weight gradient from those reads into nin_c's slab)
-  const WgradHead hd{head_gnb ? OC : 0, dyv.p, dyv.stride, prm + p.P.L[NINC].woff,
-                     fold_c ? SL(NINC) + 64 : nullptr, G(NINC)};
-  DN_TRY(wgrad(W_C1, head_gnb ? V(p.nb, 96) : V(p.g_nb, 96), V(p.na, 96), N, H(0), Wd(0), 96, 96,
-               G(NINB), SL(NINB), p.splits[NINB], s2, x6, Z, &rb, &hd));
-  DN_TRY(fork());
-  DN_TRY(wgrad(W_C1, V(p.g_na, 96), V(p.d1b, 96), N, H(0), Wd(0), 96, 96, G(NINA), SL(NINA),
-               p.splits[NINA], s2, x6, Z, &rb));
-  DN_TRY(fork());
+  DN_TRY(bs.fork());
   DN_TRY(wgrad(W_C3, V(p.g_d1b, 96), V(p.d1a, 96), N, H(0), Wd(0), 96, 96, G(D1B), SL(D1B),
-               p.splits[D1B], s2, x6w, Z, &rb));
+               p.splits[D1B], bs.s2, x6, Z, &bs.rb));
   DN_TRY(conv_dgrad(D1B, V(p.g_d1b, 96), EPI_MASK, V(p.d1a, 96), V(p.g_d1a, 96), s));
-  // dec_conv1a weight gradient: the MFMA kernel over the up1 channels [0, 2nf) and the thin
-  // kernel over the network-input channels [2nf, 2nf + C), each into its own slab rows and
-  // reduced into its own columns of W[co][c1k][9]
-  {
-    const long n = (long)96 * p.c1k * 9 + 96;
-    float* slab = SL(D1A) + 64;
-    WgradArgs a{};
-    a.g = ws + p.g_d1a; a.g_stride = 96; a.g_off = 0;
-    a.x = ws + p.c1; a.x_stride = p.c1s; a.x_off = 0;
-    a.N = N; a.KH = H(0); a.KW = Wd(0); a.Cout = 96; a.Cin = 2 * nf;
-    a.zeros = Z; a.slab = slab; a.slab_stride = n;
-    a.wlayout = 0; a.cin_total = p.c1k; a.ci_base = 0; a.bias = 1;
-    const int sp = x6w ? wgrad_splits_x6(a, p.splits[D1A]) : p.splits[D1A];
-    DN_TRY(fork());
-    DN_TIMED(s2, "wgrad3", 2.0 * N * H(0) * Wd(0) * 96 * 2 * nf * 9, 2 * nf, 96, H(0), Wd(0), N,
-             launch_wgrad(W_C3, a, sp, s2, x6w));
-    RedJob j = red_job(slab, n, sp, 96L * 2 * nf * 9, G(D1A));  // W[co][ci < 2nf][t]
-    j.ig = j.og = 2 * nf * 9;
-    j.is1 = j.os1 = p.c1k * 9;
-    DN_TRY(red_add(&rb, j, s2));  // (a full batch flushes on s2, behind the wgrads it reads)
-    DN_TRY(red_add(&rb, red_job(slab + 96L * p.c1k * 9, n, sp, 96, G(D1A) + 96L * p.c1k * 9), s2));
-    // input-channel slice: compact [co][C][9] rows after the MFMA kernel's, own split count,
-    // scattered into W[co][2nf + ci][t]
-    float* thin = slab + (long)p.splits[D1A] * n;
-    const long nt = 96L * C * 9;
-    const int st = enc0_wgrad_splits(N, H(0), Wd(0));
-    DN_TIMED(s2, "wgrad3_thin", 2.0 * N * H(0) * Wd(0) * 96 * C * 9, C, 96, H(0), Wd(0), N,
-             launch_wgrad_c3_thin(ws + p.g_d1a, 96, ws + p.xin, N, C, H(0), Wd(0), thin, nt, C, 0,
-                                  0, st, s2));
-    DN_TRY(launch_reduce_scatter(thin, nt, st, nt, G(D1A), 9L * C, 9L * p.c1k, 9L * 2 * nf, s2,
-                                 &rb));
-  }
+  // dec_conv1a's weight gradient: up1's channels [0, 2nf) and the network input's [2nf, 2nf + C)
+  if (dn_status st = d1a_wgrad(bs, tail, ws + p.g_d1a, V(p.c1, p.c1s), p.c1k, ws + p.xin, C, dst(D1A)))
+    return st;
   // only the up1 part of the concat needs a gradient (pool0 is the network input)
   DN_TRY(conv_dgrad(D1A, V(p.g_d1a, 96), EPI_PLAIN, none, V(p.g_c1, 2 * nf), s));
 
@@ -1078,41 +753,40 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   for (int l = 1; l <= 4; ++l) {
     const int iu = up_idx[l - 1];  // deconv producing level l-1 from level l
     // deconv wgrad: x = d_l b (level l), dU at level l-1
-    DN_TRY(fork());
+    DN_TRY(bs.fork());
     DN_TRY(wgrad(W_UP2, dU, V(p.db[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf, G(iu), SL(iu),
-                 p.splits[iu], s2, x6, Z, &rb));
+                 p.splits[iu], bs.s2, x6, Z, &bs.rb));
     DN_TRY(deconv_dgrad(iu, dU, V(p.db[l], 2 * nf), EPI_MASK, V(p.g_db[l], 2 * nf), s));
     const int ia = da_idx[l], ib = ia + 1;
-    DN_TRY(fork());
+    DN_TRY(bs.fork());
     DN_TRY(wgrad(W_C3, V(p.g_db[l], 2 * nf), V(p.da[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf,
-                 G(ib), SL(ib), p.splits[ib], s2, x6w, Z, &rb));
+                 G(ib), SL(ib), p.splits[ib], bs.s2, x6, Z, &bs.rb));
     DN_TRY(conv_dgrad(ib, V(p.g_db[l], 2 * nf), EPI_MASK, V(p.da[l], 2 * nf), V(p.g_da[l], 2 * nf),
                       s));
-    DN_TRY(fork());
+    DN_TRY(bs.fork());
     // channel count ck (the layer's cin, what G(ia) and the dgrad pack are sized for); cs is
     // only the pixel stride (larger under a DN_C1S_ALIGN override)
     DN_TRY(wgrad(W_C3, V(p.g_da[l], 2 * nf), V(p.c[l], p.cs[l]), N, H(l), Wd(l), 2 * nf, p.ck[l],
-                 G(ia), SL(ia), p.splits[ia], s2, x6w, Z, &rb));
+                 G(ia), SL(ia), p.splits[ia], bs.s2, x6, Z, &bs.rb));
     DN_TRY(conv_dgrad(ia, V(p.g_da[l], 2 * nf), EPI_PLAIN, none, V(p.g_c[l], p.cs[l]), s));
     dU = V(p.g_c[l], p.cs[l], 0);  // [u_{l+1} grad | skip grad]
   }
   // the head's and the decoder's reductions on the side stream now, behind their weight
   // gradients, overlapping the encoder's data gradients
-  if (side) {
-    DN_TIMED(side->rst, "reduce", 0, 0, 0, 0, 0, 0, flush_side());
-    // dprm[tail_begin ..] (dec_conv5a .. nin_c) is final behind this flush
-    if (tail_ready) DN_TRY(hipEventRecord(tail_ready, side->rst));
+  DN_TRY(bs.flush_reductions());
+  if (bs.side && tail_ready) {  // dprm[tail_begin ..] (dec_conv5a .. nin_c) is final behind this flush
+    DN_TRY(hipEventRecord(tail_ready, bs.side->rst));
     tail_ready = nullptr;
   }
   // up5: x = a6 (level 5), dU = g_c5[0:nf]
-  DN_TRY(fork());
+  DN_TRY(bs.fork());
   DN_TRY(wgrad(W_UP2, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), N, H(5), Wd(5), nf, nf, G(UP5), SL(UP5),
-               p.splits[UP5], s2, false, Z, &rb));
+               p.splits[UP5], bs.s2, false, Z, &bs.rb));
   DN_TRY(deconv_dgrad(UP5, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), EPI_MASK, V(p.g_a6, nf), s));
   // enc_conv6 (input p5, level 5)
-  DN_TRY(fork());
+  DN_TRY(bs.fork());
   DN_TRY(wgrad(W_C3, V(p.g_a6, nf), V(p.p5, nf), N, H(5), Wd(5), nf, nf, G(ENC6), SL(ENC6),
-               p.splits[ENC6], s2, x6w, Z, &rb));
+               p.splits[ENC6], bs.s2, x6, Z, &bs.rb));
   DN_TRY(conv_dgrad(ENC6, V(p.g_a6, nf), EPI_PLAIN, none, V(p.g_p5, nf), s));
   // pool5 backward -> g_a5 (level 4)
   DN_TIMED(s, "pool_bwd", 0, 0, 0, 0, 0, 0, launch_pool_bwd(ws + p.a[4], N, H(4), Wd(4), nf, ws + p.g_p5, nf, 0, 1, ws + p.g_a[4], s));
@@ -1120,9 +794,9 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   for (int l = 4; l >= 1; --l) {
     const int li = ENC2 + (l - 1);
     const int skip = (l == 4) ? nf : 2 * nf;
-    DN_TRY(fork());
+    DN_TRY(bs.fork());
     DN_TRY(wgrad(W_C3, V(p.g_a[l], nf), V(p.c[l], p.cs[l], skip), N, H(l), Wd(l), nf, nf, G(li),
-                 SL(li), p.splits[li], s2, x6w, Z, &rb));
+                 SL(li), p.splits[li], bs.s2, x6, Z, &bs.rb));
     DN_TRY(conv_dgrad(li, V(p.g_a[l], nf), EPI_ACCUM, none, V(p.g_c[l], p.cs[l], skip), s));
     // pool_l backward: d p_l (skip slice) -> gradient of the level l-1 activation
     if (l > 1) {
@@ -1136,26 +810,21 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   // the encoder's deep-level reductions (up5, enc_conv6 .. enc_conv2) on the side stream now,
   // beside enc_conv1's data gradient, so the serial tail of the step (after the last data
   // gradient) only reduces enc_conv1's and enc_conv0's slabs
-  if (side) DN_TIMED(side->rst, "reduce", 0, 0, 0, 0, 0, 0, flush_side());
+  DN_TRY(bs.flush_reductions());
   // enc_conv1 (input a0), enc_conv0 (input x = c1 slice; no data gradient needed).  Two
   // streams: enc_conv1's weight gradient on the main stream behind its data gradient and
   // enc_conv0's beside it on the side stream, which is still working through the encoder's
   // weight gradients (both streams end together instead of the side stream alone for ~0.5 ms,
   // profiles/r6_step_timeline.txt)
   DN_TRY(conv_dgrad(ENC1, V(p.g_a1, nf), EPI_MASK, V(p.a0, nf), V(p.g_a0, nf), s));
-  DN_TRY(fork());
-  DN_TIMED(s2, "wgrad3_thin", 2.0 * N * H(0) * Wd(0) * nf * C * 9, C, nf, H(0), Wd(0), N,
+  DN_TRY(bs.fork());
+  DN_TIMED(bs.s2, "wgrad3_thin", 2.0 * N * H(0) * Wd(0) * nf * C * 9, C, nf, H(0), Wd(0), N,
            launch_enc0_wgrad(ws + p.g_a0, nf, ws + p.xin, N, C, H(0), Wd(0), SL(ENC0) + 64,
-                             p.splits[ENC0], G(ENC0), s2, &rb));
+                             p.splits[ENC0], G(ENC0), bs.s2, &bs.rb));
   DN_TRY(wgrad(W_C3, V(p.g_a1, nf), V(p.a0, nf), N, H(0), Wd(0), nf, nf, G(ENC1), SL(ENC1),
-               p.splits[ENC1], s, x6w, Z, &rb));
-  if (side) {  // join the weight-gradient and reduction branches before the last reduction
-    DN_TRY(hipEventRecord(side->join, s2));
-    DN_TRY(hipStreamWaitEvent(s, side->join, 0));
-    DN_TRY(hipEventRecord(side->rjoin, side->rst));
-    DN_TRY(hipStreamWaitEvent(s, side->rjoin, 0));
-  }
-  DN_TIMED(s, "reduce", 0, 0, 0, 0, 0, 0, red_flush(rb, s));
+               p.splits[ENC1], s, x6, Z, &bs.rb));
+  DN_TRY(bs.join());  // the weight-gradient and reduction branches, before the last reduction
+  DN_TIMED(s, "reduce", 0, 0, 0, 0, 0, 0, red_flush(bs.rb, s));
   if (tail_ready) DN_TRY(hipEventRecord(tail_ready, s));  // one stream: everything is final here
   // dL/dx: the network input feeds enc_conv0 and (as pool0) dec_conv1a's last C channels
   if (dx)

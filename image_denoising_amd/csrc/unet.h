@@ -1,9 +1,9 @@
-// Host-side U-Net plan and orchestration (internal).
+// Host-side U-Net plan and orchestration (internal).  The network-independent helpers, the side
+// streams and the tail shared with the RESNET are declared in exec_common.h.
 #pragma once
 #include <string>
 
-#include "../../include/denoise_hip.h"
-#include "dn_internal.h"
+#include "exec_common.h"
 
 namespace dn {
 
@@ -13,18 +13,10 @@ enum LayerIdx {
   NINA, NINB, NINC, NL
 };
 
-struct Layer {
-  int cout, cin, k;
-  bool deconv;   // ConvTranspose2d: weight [cin][cout][2][2]
-  long woff;     // float offset of the weight in the flat buffer (bias follows)
-  long wcount;
-};
-
 struct ParamLayout {
   Layer L[NL];
   long total;
 };
-
 
 struct Plan {
   ParamLayout P;
@@ -65,8 +57,6 @@ struct Plan {
   long total_floats;
 };
 
-void set_error(const std::string& s);
-extern thread_local std::string g_last_error;
 const char* layer_name(int i);
 int layer_level(int i);
 int dgrad_nout(const Plan& p, int i);
@@ -90,59 +80,6 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
                         float* ws, hipStream_t s, int prec = DN_PREC_FP32,
                         hipEvent_t tail_ready = nullptr);
 // first float of the parameter range the backward finishes early (dec_conv5a .. nin_c)
-// The backward's side streams (unet.cpp): weight gradients on `st`, slab reductions on `rst`,
-// with their fork / join events; one set per host thread and device (nullptr when creating them
-// failed: run on one stream).  Shared by the UNet and ImprovedUNet executors.
-struct SideStream {
-  hipStream_t st = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  // the slab reductions' own stream (round 6): a flush there overlaps both the data-gradient
-  // chain and the remaining weight gradients instead of delaying the latter on `st`
-  hipStream_t rst = nullptr;
-  hipEvent_t rfork = nullptr, rjoin = nullptr;
-};
-SideStream* side_stream(hipStream_t s);
-bool bwd_two_streams();  // false under DN_BWD_STREAMS=0: the backward on one stream
-// the side stream continues after the work queued on s so far (side == nullptr: nothing to do)
-hipError_t side_fork(SideStream* side, hipStream_t s);
-
 long tail_begin(const Plan& p);
-// zc of the bf16x6 data gradient of a 3x3 layer producing nout channels (0: one block)
-int x6_dgrad_zc(int nout);
-
-WView conv_fwd_view(const float* w, int K, int ksize);
-WView conv_dgrad_view(const float* w, int cin_total, int ksize);
-WView deconv_fwd_view(const float* w, int cout);
-WView deconv_dgrad_view(const float* w, int cout);
-long conv_fwd_pack_size(int K, int cout, int ksize);
-long conv_dgrad_pack_size(int cout, int nout, int ksize);
-long deconv_fwd_pack_size(int cin, int cout);
-long deconv_dgrad_pack_size(int cout, int cin);
-hipError_t pack_conv_fwd(const float* w, int K, int cout, int ksize, float* out, hipStream_t s);
-hipError_t pack_conv_dgrad(const float* w, int cin_total, int nout, int cout, int ksize, float* out,
-                           hipStream_t s);
-hipError_t pack_deconv_fwd(const float* w, int cin, int cout, float* out, hipStream_t s);
-hipError_t pack_deconv_dgrad(const float* w, int cout, int cin, float* out, hipStream_t s);
-hipError_t conv_forward(const View& in, int N, int H, int W, int K, const float* wp,
-                        const float* b, int cout, int ksize, int act, const View& out,
-                        int out_layout, hipStream_t s);
-hipError_t conv_dgrad(const View& dz, int N, int H, int W, int cout, const float* wp, int nout,
-                      int ksize, int epi, const View& mask, const View& dx, hipStream_t s);
-hipError_t deconv_forward(const View& x, int N, int h, int w, int cin, const float* wp,
-                          const float* b, int cout, const View& out, hipStream_t s);
-hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const float* wp, int cin,
-                        const View& mask, int epi, const View& dx, hipStream_t s);
-// nin_b's weight gradient only (WgradArgs::head_gnb, hd_*): the gradient operand recomputed from
-// nb and dy, nin_c's weight gradient formed from the same reads
-struct WgradHead {
-  int gnb; const float* dy; int dy_stride; const float* wc;
-  float* slab_c; float* dwc;
-};
-// slab: [64 floats | splits x (W + b)]; zeros == nullptr: the 64 floats are zeroed here and
-// serve as the DMA padding; rb: the reduction is queued, not launched
-hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
-                 float* dwb, float* slab, int splits, hipStream_t s, bool x6 = false,
-                 const float* zeros = nullptr, RedBatch* rb = nullptr,
-                 const WgradHead* head = nullptr);
 
 }  // namespace dn
