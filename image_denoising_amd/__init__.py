@@ -12,7 +12,7 @@ from .n2n import (AugmentNoise, generate_mask_pair, generate_subimages,  # noqa:
                   n2n_loss, n2n_subsample)
 from .resnet import RESNET  # noqa: F401
 from .optim import FlatAdam, lr_at_epoch  # noqa: F401
-from .trainer import N2NTrainer, StructureTrainer  # noqa: F401
-from .util import Structure_loss  # noqa: F401
+from .trainer import N2NTrainer, StructureTrainer, SupervisedTrainer  # noqa: F401
+from .util import L1FFT, Structure_loss  # noqa: F401
 
 __version__ = "0.1.0"

@@ -90,6 +90,9 @@ SIGNATURES = {
                             c_void_p]),
     "dn_structure_loss": (c_int, [_F, _F, _F, c_int, c_int, c_int, c_int, c_float, c_float,
                                   c_float, _F, _F, _F, c_void_p, c_void_p]),
+    "dn_l1fft_ws_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dn_l1fft_loss": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_float, c_float, c_int, _F, _F,
+                              c_void_p, c_size_t, c_void_p]),
     "dn_adam_step": (c_int, [_F, _F, _F, _F, c_int64, c_float, c_float, c_float, c_float, c_int64,
                              c_float, c_void_p]),
     "dn_conv2d_pack_size": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -494,6 +494,23 @@ dn_status dn_structure_loss(const float* pred, const float* pred2, const float* 
                     "dn_structure_loss");
 }
 
+size_t dn_l1fft_ws_size(int N, int C, int H, int W) { return l1fft_ws_bytes(N, C, H, W); }
+
+dn_status dn_l1fft_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                        float alpha, float beta, int reduction_sum, float* dpred, float* loss3,
+                        void* ws, size_t ws_bytes, void* stream) {
+  const size_t need = l1fft_ws_bytes(N, C, H, W);
+  if (!need)
+    return fail(DN_ERR_ARG, "L1FFT needs N, C >= 1 and H, W powers of two in [8, 1024]");
+  if (!pred || !target || !dpred || !loss3 || !ws) return fail(DN_ERR_ARG, "null argument");
+  if (reinterpret_cast<uintptr_t>(ws) & 15) return fail(DN_ERR_ARG, "workspace must be 16-byte aligned");
+  if (ws_bytes < need) return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_l1fft_ws_size()");
+  const OpTimer timer((hipStream_t)stream, "loss", 0);
+  return hip_status(launch_l1fft_loss(pred, target, N, C, H, W, alpha, beta, reduction_sum != 0,
+                                      dpred, loss3, ws, (hipStream_t)stream),
+                    "dn_l1fft_loss");
+}
+
 // The double a caller wrote before the ABI narrowed it to fp32: the shortest decimal that rounds
 // to x.  torch.optim.Adam keeps lr and the betas as Python doubles and forms 1 - beta, beta^step
 // and lr / bc1 from those.  (double)0.999f is 0.99900001287..., and 1 - beta2 formed from it is

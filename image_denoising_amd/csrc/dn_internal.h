@@ -424,6 +424,11 @@ hipError_t launch_structure_loss(const float* pred, const float* pred2, const fl
                                  int C, int H, int W, float alpha, float beta, float gamma,
                                  float* dpred, float* dpred2, float* loss5, void* partials,
                                  hipStream_t s);
+// ---- L1FFT (fft_loss.hip): H, W powers of two in [8, 1024]; ws = l1fft_ws_bytes() (0: unsupported)
+size_t l1fft_ws_bytes(int N, int C, int H, int W);
+hipError_t launch_l1fft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
+                             float alpha, float beta, bool reduction_sum, float* dpred,
+                             float* loss3, void* ws, hipStream_t s);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float w1,
                        float b2, float w2, float step_size, float bc2s, float eps, float gscale,
                        hipStream_t s);

@@ -24,9 +24,9 @@ import torch
 from . import _lib
 from . import dist as dp
 from .arch_unet import UNet
-from .n2n import AugmentNoise, n2n_loss, n2n_subsample
+from .n2n import AugmentNoise, _partials_for, n2n_loss, n2n_subsample
 from .optim import FlatAdam, lr_at_epoch
-from .util import structure_loss_into
+from .util import l1fft_loss_into, l1fft_supported, structure_loss_into
 
 
 class N2NTrainer:
@@ -225,3 +225,70 @@ class StructureTrainer:
         self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
         self.opt.step(self.grad, grad_scale=scale)
         return b["loss5"].clone()
+
+
+class SupervisedTrainer:
+    """The plain supervised step `criterion(network(noisy), clean)` (train.py:362 with the
+    criterion of train.py:318-321; train_opt.py:122-157 without its guards), fused:
+
+        pred = net(noisy)                   [saved]   _run_forward
+        loss3, dpred = criterion(pred, clean)         dn_l1fft_loss ('l1fft', util.py:5-38)
+                                                      dn_finetune_loss at lambda 0 ('l1')
+        dW = backward(dpred)                          _run_backward
+        [data parallel: one RCCL all-reduce(sum) of dW]
+        Adam(W, dW / world)                           dn_adam_step
+
+    One forward and one backward of N images (StructureTrainer with weights (1, 0, 0) gives the
+    same loss from a 2N batch whose second half gets zero gradient).  net: UNet, RESNET or
+    ImprovedUNet.  'l1fft' needs H and W powers of two in [8, 1024]; alpha and beta are its
+    weights ('l1' is nn.L1Loss and takes neither).
+    Returns loss3 = [pixel L1, spectrum L1 (0 for 'l1'), total] (device tensor).
+    """
+
+    def __init__(self, net, criterion: str = "l1fft", alpha: float = 1.0, beta: float = 1.0,
+                 lr: float = 3e-4, n_epoch: int = 100, gamma: float = 0.5,
+                 distributed: bool | None = None):
+        if criterion not in ("l1", "l1fft"):
+            raise ValueError("criterion must be 'l1' or 'l1fft'")
+        self.net = net
+        self.criterion, self.alpha, self.beta = criterion, alpha, beta
+        self.base_lr, self.n_epoch, self.gamma = lr, n_epoch, gamma
+        self.distributed = dp.require_group(distributed)
+        if self.distributed:
+            dp.broadcast_params(net.flat_params)
+        self.opt = FlatAdam(net.flat_params, lr=lr)
+        self.grad = torch.zeros_like(net.flat_params)
+        self._bufs = {}
+
+    def _buffers(self, N, H, W, device):
+        key = (N, H, W, device)
+        if key not in self._bufs:
+            f = dict(dtype=torch.float32, device=device)
+            self._bufs = {key: dict(
+                pred=torch.empty((N, self.net.out_nc, H, W), **f),
+                dpred=torch.empty((N, self.net.out_nc, H, W), **f),
+                loss3=torch.empty(3, **f),
+                ws=self.net._workspace(N, H, W, with_backward=True, fresh=True))}
+        return self._bufs[key]
+
+    def train_step(self, clean: torch.Tensor, noisy: torch.Tensor, epoch: int = 1) -> torch.Tensor:
+        clean, noisy = clean.contiguous(), noisy.contiguous()
+        N, C, H, W = noisy.shape
+        if C != self.net.in_nc or clean.shape != (N, self.net.out_nc, H, W):
+            raise ValueError("noisy must be [N, in_nc, H, W] and clean [N, out_nc, H, W]")
+        if self.criterion == "l1fft" and not l1fft_supported(H, W):
+            raise ValueError(f"L1FFT needs H and W powers of two in [8, 1024], got {H} x {W}")
+        b = self._buffers(N, H, W, clean.device)
+        self.net._run_forward(noisy, b["pred"], b["ws"])
+        if self.criterion == "l1fft":
+            l1fft_loss_into(b["pred"], clean, self.alpha, self.beta, b["dpred"], b["loss3"])
+        else:
+            _lib.call("dn_finetune_loss", _lib.ptr(b["pred"]), _lib.ptr(clean), N,
+                      self.net.out_nc, H, W, 0.0, _lib.ptr(b["dpred"]), _lib.ptr(b["loss3"]),
+                      _partials_for(clean.device).data_ptr(), _lib.stream_of(clean))
+            b["loss3"][1].zero_()  # the unweighted gradient-L1 the kernel also reports
+        self.net._run_backward(b["dpred"], self.grad, b["ws"], N, H, W)
+        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
+        self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
+        self.opt.step(self.grad, grad_scale=scale)
+        return b["loss3"].clone()

@@ -2,6 +2,10 @@
 
 L = alpha*L1(pred, target) + beta*(L1(pred2[:,:,1:],pred2[:,:,:-1]) + L1(pred2[...,1:],pred2[...,:-1]))/2
     + gamma*L1(pred2, target)      with pred = net(noisy), pred2 = net(clean) (train.py:361-363)
+
+and L1FFT (util.py:5-38), by the row / column / row FFT kernels of csrc/fft_loss.hip:
+
+L = alpha*L1(pred, target) + beta*mean|fft2(pred) - fft2(target)|      (train.py:318-321)
 """
 from __future__ import annotations
 
@@ -62,3 +66,79 @@ class Structure_loss(nn.Module):  # noqa: N801  (reference name, util.py:41)
 
     def forward(self, pred, pred2, target):
         return _StructureFn.apply(pred, pred2, target, self.alpha, self.beta, self.gamma)
+
+
+# ---- L1FFT (util.py:5-38 of the reference) -------------------------------------------------
+_l1fft_ws = {}
+
+
+def l1fft_supported(H: int, W: int) -> bool:
+    """the transform lengths dn_l1fft_loss has: powers of two from 8 to 1024"""
+    return all(8 <= v <= 1024 and v & (v - 1) == 0 for v in (int(H), int(W)))
+
+
+def _l1fft_ws_for(N, C, H, W, device) -> torch.Tensor:
+    """the loss's workspace (half spectrum + block partials), one per device, grown on demand"""
+    need = _lib.lib().dn_l1fft_ws_size(N, C, H, W)
+    t = _l1fft_ws.get(device)
+    if t is None or t.numel() < need:
+        t = _lib.scratch(need, device)
+        _l1fft_ws[device] = t
+    return t
+
+
+def l1fft_loss_into(pred, target, alpha, beta, dpred, loss3, reduction="mean"):
+    """dn_l1fft_loss into given contiguous buffers: loss3 = [pixel, freq, total],
+    dpred = dL/dpred (all on pred's device and stream).  H and W must be powers of two in
+    [8, 1024]: anything else raises ValueError (there is no other path)."""
+    if reduction not in ("mean", "sum"):
+        raise NotImplementedError("L1FFT supports reduction='mean' and 'sum'")
+    for t in (pred, target, dpred, loss3):
+        if not t.is_contiguous():
+            raise ValueError("l1fft_loss_into needs contiguous tensors")
+    if (pred.dim() != 4 or pred.shape != target.shape or dpred.shape != pred.shape
+            or loss3.numel() != 3):
+        raise ValueError("pred, target and dpred must share one [N,C,H,W] shape, loss3 holds 3")
+    N, C, H, W = pred.shape
+    if N < 1 or C < 1 or not l1fft_supported(H, W):
+        raise ValueError(f"L1FFT needs H and W powers of two in [8, 1024], got {H} x {W}")
+    ws = _l1fft_ws_for(N, C, H, W, pred.device)
+    _lib.call("dn_l1fft_loss", _lib.ptr(pred), _lib.ptr(target), N, C, H, W, float(alpha),
+              float(beta), int(reduction == "sum"), _lib.ptr(dpred), _lib.ptr(loss3),
+              ws.data_ptr(), ws.numel(), _lib.stream_of(pred))
+
+
+def l1fft_loss(pred, target, alpha=1.0, beta=1.0, reduction="mean"):
+    """returns (loss3 = [pixel, freq, total] device tensor, dpred)"""
+    pred, target = pred.contiguous(), target.contiguous()
+    dpred = torch.empty_like(pred)
+    loss3 = torch.empty(3, dtype=torch.float32, device=pred.device)
+    l1fft_loss_into(pred, target, alpha, beta, dpred, loss3, reduction)
+    return loss3, dpred
+
+
+class _L1FFTFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, alpha, beta, reduction):
+        loss3, dp = l1fft_loss(pred, target, alpha, beta, reduction)
+        ctx.save_for_backward(dp)
+        return loss3[2]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dp,) = ctx.saved_tensors
+        return dp * g, None, None, None, None
+
+
+class L1FFT(nn.Module):  # reference name, util.py:5
+    """alpha * L1(pred, target) + beta * |fft2(pred) - fft2(target)| reduced like the L1 term.
+    The gradient flows to pred only (the target is data), as for the other losses here."""
+
+    def __init__(self, alpha: float = 1.0, beta: float = 1.0, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise NotImplementedError("L1FFT supports reduction='mean' and 'sum', not 'none'")
+        self.alpha, self.beta, self.reduction = alpha, beta, reduction
+
+    def forward(self, pred, target):
+        return _L1FFTFn.apply(pred, target, self.alpha, self.beta, self.reduction)

@@ -247,6 +247,17 @@ dn_status dn_n2n_loss(const float* out, const float* sub2, const float* den, con
 dn_status dn_structure_loss(const float* pred, const float* pred2, const float* target, int N, int C,
                             int H, int W, float alpha, float beta, float gamma, float* dpred,
                             float* dpred2, float* loss5, void* partial_ws, void* stream);
+/* L1FFT, util.py:5-38: L = alpha*L1(pred,tgt) + beta*mean|fft2(pred) - fft2(tgt)| (fft2 over the
+   last two dimensions, unnormalised, mean over the full H x W spectrum of every plane;
+   reduction_sum != 0: both means become sums).  H and W must be powers of two in [8, 1024]
+   (anything else: DN_ERR_ARG, there is no other path).  Writes dpred = dL/dpred (spectrum bins of
+   magnitude 0 contribute no gradient, as torch's complex abs) and loss3 = {pixel, freq, total}
+   (device floats).  beta == 0 runs no transform.  ws: 16-byte aligned, dn_l1fft_ws_size() bytes
+   (0 for an unsupported shape); a smaller ws_bytes is DN_ERR_WORKSPACE. */
+size_t dn_l1fft_ws_size(int N, int C, int H, int W);
+dn_status dn_l1fft_loss(const float* pred, const float* target, int N, int C, int H, int W,
+                        float alpha, float beta, int reduction_sum, float* dpred, float* loss3,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* ---- optimiser: torch.optim.Adam as used at train.py:332, :368 --------------------- */
 /* One fused Adam step over n floats (torch _single_tensor_adam math, amsgrad=False,
