@@ -501,7 +501,7 @@ dn_status dn_l1fft_loss(const float* pred, const float* target, int N, int C, in
                         void* ws, size_t ws_bytes, void* stream) {
   const size_t need = l1fft_ws_bytes(N, C, H, W);
   if (!need)
-    return fail(DN_ERR_ARG, "L1FFT needs N, C >= 1 and H, W powers of two in [8, 1024]");
+    return fail(DN_ERR_ARG, "L1FFT needs N, C >= 1 and H, W = m * 2^k with m odd <= 31, k >= 3, at most 1024");
   if (!pred || !target || !dpred || !loss3 || !ws) return fail(DN_ERR_ARG, "null argument");
   if (reinterpret_cast<uintptr_t>(ws) & 15) return fail(DN_ERR_ARG, "workspace must be 16-byte aligned");
   if (ws_bytes < need) return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_l1fft_ws_size()");

@@ -424,7 +424,8 @@ hipError_t launch_structure_loss(const float* pred, const float* pred2, const fl
                                  int C, int H, int W, float alpha, float beta, float gamma,
                                  float* dpred, float* dpred2, float* loss5, void* partials,
                                  hipStream_t s);
-// ---- L1FFT (fft_loss.hip): H, W powers of two in [8, 1024]; ws = l1fft_ws_bytes() (0: unsupported)
+// ---- L1FFT (fft_loss.hip): H, W = m * 2^k with m odd <= 31, k >= 3, at most 1024;
+// ws = l1fft_ws_bytes() (0: unsupported)
 size_t l1fft_ws_bytes(int N, int C, int H, int W);
 hipError_t launch_l1fft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
                              float alpha, float beta, bool reduction_sum, float* dpred,

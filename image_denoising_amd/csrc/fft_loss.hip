@@ -9,12 +9,23 @@
 //   k_l1fft_rows_inv   half-spectrum -> real inverse along W, dpred = ga * sgn(D) + gb * result
 //   k_l1fft_finalize   fixed-order sum of the per-block fp64 partials -> loss3
 //
-// Every transform is radix-2 over an LDS tile whose fastest index is the batch lane (a spectrum
-// column / a row pair), so the 32 lanes of an LDS lane group read one contiguous 256-byte bank
-// row at every butterfly stride.  The forward is decimation in frequency (natural in, bit-reversed
-// out) and the inverse decimation in time (bit-reversed in, natural out): the column pass needs
-// no reordering at all, the row passes reverse bits while they unpack / pack the row pair.
-// Twiddles are sincospi in fp64, rounded once to fp32, per block in LDS.
+// A transform length is L = m P with m odd, 1 <= m <= 31, and P = 2^k >= 8 (L <= 1024): one
+// Cooley-Tukey split in front of a radix-2 network.  With input index n = P n1 + n2 and output
+// bin k = k1 + m k2 the forward is (a) the m-point DFT over n1 of the rows n1 P + n2, times the
+// twiddle exp(-2 pi i n2 k1 / L), to row k1 P + n2, then (b) radix-2 decimation in frequency
+// inside every aligned block of P rows, which leaves bin k at row
+//     pos(k) = (k mod m) P + brev_P(k div m).
+// The inverse is the transpose: radix-2 decimation in time per block (bins at pos(k) in), the
+// conjugate twiddles, the unnormalised inverse m-point DFT, natural order out.  m = 1 skips (a)
+// and is the plain radix-2 transform.  The column pass applies |F| and F / |F| pointwise and
+// needs no reordering at all; the row passes place bins by pos(k) while they unpack / pack the
+// row pair.
+//
+// The LDS tile's fastest index is the batch lane (a spectrum column / a row pair), so the 32 lanes
+// of an LDS lane group read one contiguous 256-byte bank row at every butterfly stride.
+// Twiddles are one table tw[j] = exp(-2 pi i j / L), j < L: sincospi in fp64, rounded once to
+// fp32, per block in LDS.  The radix-2 stages read it at multiples of m, the odd stage's twiddle
+// is tw[n2 k1] (n2 k1 < L) and its m-point DFT matrix tw[(n1 k1 mod m) P].
 #include <hip/hip_runtime.h>
 
 #include "dn_internal.h"
@@ -25,23 +36,30 @@ namespace {
 constexpr int kFftTile = 4096;      // complex elements of a tile: batch lanes x transform length
 constexpr int kFftLds = 5120;       // ... plus the row passes' one-lane row padding (L = 1024)
 constexpr int kFftMaxL = 1024;
+constexpr int kFftMaxOdd = 31;      // the odd factor m of L
 
 // One LDS tile of TC batch lanes x L points: element (h, c) at s[slot(h) * pitch + c].
-// TC = min(32, kFftTile / L).  With TC < 32 an LDS lane group of 32 holds G = 32 / TC butterflies
-// whose rows must fall on different 1/G-ths of the 64 banks: slot() mirrors the low bits of every
-// odd aligned block of G rows, after which the rows a group touches at any stage (r .. r+G-1 for
-// half-size m >= G, every 2m-th pair inside one aligned 2G block below) take G distinct values
-// mod G.  The row passes pad the pitch by one lane so that their transposed fill (consecutive
-// lanes = consecutive h) is conflict-free as well.
+// TC = the largest power of two <= min(32, kFftTile / L).  With TC < 32 an LDS lane group of 32
+// holds G = 32 / TC butterflies whose rows must fall on different 1/G-ths of the 64 banks: slot()
+// mirrors the low bits of every odd aligned block of G rows, after which the rows a group touches
+// at any stage (r .. r+G-1 for half-size >= G, every pair inside one aligned 2G block below)
+// take G distinct values mod G.  slot() permutes rows inside aligned blocks of 2G rows, and 2G
+// divides P (so every accepted L, and every block of P rows) wherever G > 1: G > 1 means L > 128,
+// which with m <= 31 forces P >= 8 = 2G at G <= 4, and G = 8 means L > 512, which forces P >= 32.
+// The row passes pad the pitch by one lane so that their transposed fill (consecutive lanes =
+// consecutive h) is conflict-free as well.
 struct FftTile {
-  int L, logL, TC, logTC, pitch, g, gm;
+  int L, mo, P, logP, TC, logTC, pitch, g, gm;  // L = mo * P, mo odd, P = 1 << logP
 };
 
 FftTile fft_tile_for(int L, int pad) {
   FftTile t{};
   t.L = L;
-  while ((1 << t.logL) < L) ++t.logL;
-  t.TC = kFftTile / L < 32 ? kFftTile / L : 32;
+  while (((L >> t.logP) & 1) == 0) ++t.logP;
+  t.P = 1 << t.logP;
+  t.mo = L >> t.logP;
+  t.TC = 32;
+  while (t.TC * L > kFftTile) t.TC >>= 1;
   while ((1 << t.logTC) < t.TC) ++t.logTC;
   t.pitch = t.TC + pad;
   const int G = 32 / t.TC;
@@ -54,35 +72,127 @@ __device__ __forceinline__ int fft_slot(int h, const FftTile& t) {
   return h ^ (((h >> t.g) & 1) * t.gm);
 }
 
-__device__ __forceinline__ int fft_brev(int k, int logL) {
-  return (int)(__brev((unsigned)k) >> (32 - logL));
+// the row of bin k after the forward transform (and where the inverse expects it)
+__device__ __forceinline__ int fft_pos(int k, const FftTile& t) {
+  const int k2 = k / t.mo, k1 = k - k2 * t.mo;
+  return (k1 << t.logP) + (int)(__brev((unsigned)k2) >> (32 - t.logP));
 }
 
-// tw[k] = exp(-2 pi i k / L), k < L / 2 (2k / L is exact: L is a power of two)
+// tw[j] = exp(-2 pi i j / L), j < L
 __device__ __forceinline__ void fft_twiddles(float2* tw, int L) {
-  for (int k = threadIdx.x; k < L / 2; k += 256) {
+  for (int k = threadIdx.x; k < L; k += 256) {
     double sn, cs;
     sincospi(-2.0 * (double)k / (double)L, &sn, &cs);
     tw[k] = make_float2((float)cs, (float)sn);
   }
 }
 
-// INV = false: forward DIF, X[k] left at point brev(k).  INV = true: unnormalised inverse DIT of
-// a spectrum stored at brev(k), natural order out.  The caller synchronises before the call; the
-// tile is synchronised on return.
+// The odd stage: thread = (n2 < P, batch lane c), its M points rows j P + n2 in registers.
+// The M-point DFT is direct, in its real-symmetric form: with a_j = x_j + x_{M-j},
+// b_j = x_j - x_{M-j}, c = cos(2 pi j k / M), s = sin(2 pi j k / M) for j, k = 1 .. (M-1)/2,
+//     y_k, y_{M-k} = x_0 + sum_j a_j c  -/+  i sum_j b_j s        (+/- for the inverse)
+// which is (M-1)^2 real multiply-adds instead of 4 M^2.  The loop over j is unrolled over the
+// compile-time M, so x, a, b are registers at constant indices; the loop over k is a real loop,
+// and cos, sin of (j k mod M) come from the table row r P = (cos, -sin)(2 pi r / M), r stepped
+// by k mod M: one address per wave, an LDS broadcast.  No array is indexed dynamically.
+// Forward: y_k times tw[n2 k] to row k P + n2.  Inverse: x_k = row k P + n2 times conj tw[n2 k]
+// on load.  A thread reads and writes the same M elements: no barrier inside the stage.
+// LDS banks (derived by the 64-bank rule, not measured): a 32-lane group covers G consecutive n2
+// of TC lanes each, which slot() keeps inside one aligned block of G rows; in the column pass
+// (pitch TC) these are 256 contiguous bytes, conflict-free for loads and stores; in the row
+// passes (pitch TC + 1) each row is shifted by two banks, so at G > 1 the last 2 (G - 1) banks of
+// the group wrap onto its first: up to G - 1 lanes two-way, conflict-free at TC = 32.  The
+// twiddle loads tw[n2 k] are G distinct addresses per group (one, broadcast, at TC = 32) at
+// banks (2 n2 k) mod 64: two of them meet only where k times their distance < G is a multiple
+// of 32, that is k = 16 at G >= 4 and k = 8, 24 at G = 8 (two-way; k = 16 at G = 8 four-way),
+// conflict-free for every other k.  The DFT-matrix loads are one address per wave (broadcast).
+template <int M, bool INV>
+__device__ __forceinline__ void fft_odd_m(float2* s, const float2* tw, const FftTile& t) {
+  constexpr int Hf = (M - 1) / 2;
+  const int ng = t.P << t.logTC;
+  for (int b = threadIdx.x; b < ng; b += 256) {
+    const int c = b & (t.TC - 1), n2 = b >> t.logTC;
+    float2 x[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      x[j] = s[fft_slot((j << t.logP) + n2, t) * t.pitch + c];
+      if (INV && j > 0) {  // times conj tw[n2 j]
+        const float2 w = tw[n2 * j], v = x[j];
+        x[j] = make_float2(v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y);
+      }
+    }
+    float2 y0 = x[0];
+#pragma unroll
+    for (int j = 1; j <= Hf; ++j) {
+      const float2 p = x[j], q = x[M - j];
+      x[j] = make_float2(p.x + q.x, p.y + q.y);      // a_j
+      x[M - j] = make_float2(p.x - q.x, p.y - q.y);  // b_j
+      y0.x += x[j].x;
+      y0.y += x[j].y;
+    }
+    s[fft_slot(n2, t) * t.pitch + c] = y0;
+#pragma unroll 1
+    for (int k = 1; k <= Hf; ++k) {
+      float2 A = x[0], B = make_float2(0.f, 0.f);
+      int r = 0;
+#pragma unroll
+      for (int j = 1; j <= Hf; ++j) {
+        r += k;
+        r -= r >= M ? M : 0;  // j k mod M
+        const float2 w = tw[r << t.logP];
+        A.x += x[j].x * w.x;
+        A.y += x[j].y * w.x;
+        B.x -= x[M - j].x * w.y;
+        B.y -= x[M - j].y * w.y;
+      }
+      // forward: y_k = A - i B, y_{M-k} = A + i B; inverse: the other way round
+      float2 yk = INV ? make_float2(A.x - B.y, A.y + B.x) : make_float2(A.x + B.y, A.y - B.x);
+      float2 ym = INV ? make_float2(A.x + B.y, A.y - B.x) : make_float2(A.x - B.y, A.y + B.x);
+      if (!INV) {  // times tw[n2 k], tw[n2 (M - k)]
+        const float2 w = tw[n2 * k], u = tw[n2 * (M - k)];
+        yk = make_float2(yk.x * w.x - yk.y * w.y, yk.x * w.y + yk.y * w.x);
+        ym = make_float2(ym.x * u.x - ym.y * u.y, ym.x * u.y + ym.y * u.x);
+      }
+      s[fft_slot((k << t.logP) + n2, t) * t.pitch + c] = yk;
+      s[fft_slot(((M - k) << t.logP) + n2, t) * t.pitch + c] = ym;
+    }
+  }
+}
+
+template <bool INV>
+__device__ __forceinline__ void fft_odd(float2* s, const float2* tw, const FftTile& t) {
+  switch (t.mo) {  // uniform over the grid
+#define DN_FFT_ODD(M) case M: fft_odd_m<M, INV>(s, tw, t); break;
+    DN_FFT_ODD(3) DN_FFT_ODD(5) DN_FFT_ODD(7) DN_FFT_ODD(9) DN_FFT_ODD(11) DN_FFT_ODD(13)
+    DN_FFT_ODD(15) DN_FFT_ODD(17) DN_FFT_ODD(19) DN_FFT_ODD(21) DN_FFT_ODD(23) DN_FFT_ODD(25)
+    DN_FFT_ODD(27) DN_FFT_ODD(29) DN_FFT_ODD(31)
+#undef DN_FFT_ODD
+    default: break;  // m = 1
+  }
+}
+
+// INV = false: forward (odd stage, then DIF per block of P rows), X[k] left at row pos(k).
+// INV = true: unnormalised inverse (DIT per block, then the odd stage) of a spectrum stored at
+// pos(k), natural order out.  The radix-2 butterflies of half-size < P stay inside aligned blocks
+// of P rows, so one index space j < L / 2 serves the m blocks at once.  The caller synchronises
+// before the call; the tile is synchronised on return.
 template <bool INV>
 __device__ __forceinline__ void fft_run(float2* s, const float2* tw, const FftTile& t) {
+  if (!INV && t.mo > 1) {
+    fft_odd<false>(s, tw, t);
+    __syncthreads();
+  }
   const int nb = (t.L >> 1) << t.logTC;
-  for (int st = 0; st < t.logL; ++st) {
-    const int lm = INV ? st : t.logL - 1 - st;
-    const int m = 1 << lm;
+  for (int st = 0; st < t.logP; ++st) {
+    const int lm = INV ? st : t.logP - 1 - st;
+    const int hs = 1 << lm;
     for (int b = threadIdx.x; b < nb; b += 256) {
       const int c = b & (t.TC - 1), j = b >> t.logTC;
-      const int i = j & (m - 1);
+      const int i = j & (hs - 1);
       const int r0 = ((j >> lm) << (lm + 1)) + i;
       float2* p0 = s + fft_slot(r0, t) * t.pitch + c;
-      float2* p1 = s + fft_slot(r0 + m, t) * t.pitch + c;
-      const float2 w = tw[i << (t.logL - 1 - lm)];
+      float2* p1 = s + fft_slot(r0 + hs, t) * t.pitch + c;
+      const float2 w = tw[(i << (t.logP - 1 - lm)) * t.mo];
       const float2 a = *p0, q = *p1;
       if (!INV) {
         const float dx = a.x - q.x, dy = a.y - q.y;
@@ -96,13 +206,18 @@ __device__ __forceinline__ void fft_run(float2* s, const float2* tw, const FftTi
     }
     __syncthreads();
   }
+  if (INV && t.mo > 1) {
+    fft_odd<true>(s, tw, t);
+    __syncthreads();
+  }
 }
 
 __device__ __forceinline__ float l1fft_sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
-// the block's sum in a fixed order -> *out (one double per block)
-__device__ __forceinline__ void l1fft_block_sum(double v, double* out) {
-  __shared__ double red[4];
+// the block's sum in a fixed order -> *out (one double per block); red: 4 doubles of LDS that no
+// thread reads or writes any more (the transform kernels lend their twiddle table, which keeps
+// the column pass at 40 KiB, four workgroups per CU)
+__device__ __forceinline__ void l1fft_block_sum(double v, double* red, double* out) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -118,14 +233,14 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_fwd(const float* __restrict_
                                                         float2* __restrict__ spec,
                                                         double* __restrict__ partials) {
   __shared__ float2 s[kFftLds];
-  __shared__ float2 tw[kFftMaxL / 2];
+  __shared__ float2 tw[kFftMaxL];
   const int Wh = W / 2 + 1;
   const long rp0 = (long)blockIdx.x * t.TC;
   fft_twiddles(tw, W);
   double acc = 0.0;
-  const int n = t.TC << t.logL;
+  const int n = t.TC * t.L;
   for (int idx = threadIdx.x; idx < n; idx += 256) {
-    const int w = idx & (W - 1), p = idx >> t.logL;
+    const int p = idx / W, w = idx - p * W;
     const long rp = rp0 + p;
     float2 v = make_float2(0.f, 0.f);
     if (rp < R) {
@@ -143,28 +258,30 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_fwd(const float* __restrict_
     const int p = idx / Wh, k = idx - p * Wh;
     const long rp = rp0 + p;
     if (rp >= R) break;  // p grows with idx
-    const float2 z1 = s[fft_slot(fft_brev(k, t.logL), t) * t.pitch + p];
-    const float2 z2 = s[fft_slot(fft_brev((W - k) & (W - 1), t.logL), t) * t.pitch + p];
+    const float2 z1 = s[fft_slot(fft_pos(k, t), t) * t.pitch + p];
+    const float2 z2 = s[fft_slot(fft_pos(k ? W - k : 0, t), t) * t.pitch + p];
     spec[(2 * rp) * Wh + k] = make_float2(0.5f * (z1.x + z2.x), 0.5f * (z1.y - z2.y));
     spec[(2 * rp + 1) * Wh + k] = make_float2(0.5f * (z1.y + z2.y), 0.5f * (z2.x - z1.x));
   }
-  l1fft_block_sum(acc, partials + blockIdx.x);
+  l1fft_block_sum(acc, reinterpret_cast<double*>(tw), partials + blockIdx.x);
 }
 
 // Block = (plane, tile of TC adjacent half-spectrum columns); the last tile of a plane is ragged
 // (W/2+1 is odd) and its missing columns are zeros, which normalise to zeros.  Column k of the
 // half spectrum stands for columns k and W-k of the full one: weight 2, but 1 for k = 0 and W/2.
-__global__ __launch_bounds__(256) void k_l1fft_cols(float2* __restrict__ spec, int H, int W,
+// waves_per_eu(4, 4): 40 KiB of LDS fit four workgroups per CU, and the odd stage (m = 31: 62
+// registers of points) stays inside the 128 registers that allows without scratch.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_l1fft_cols(float2* __restrict__ spec, int H, int W,
                                                     int ntile, FftTile t,
                                                     double* __restrict__ partials) {
   __shared__ float2 s[kFftTile];
-  __shared__ float2 tw[kFftMaxL / 2];
+  __shared__ float2 tw[kFftMaxL];
   const int Wh = W / 2 + 1;
   const int plane = blockIdx.x / ntile, tile = blockIdx.x - plane * ntile;
   const int k0 = tile * t.TC;
   float2* base = spec + (long)plane * H * Wh;
   fft_twiddles(tw, H);
-  const int n = t.TC << t.logL;
+  const int n = t.TC * t.L;
   for (int idx = threadIdx.x; idx < n; idx += 256) {
     const int c = idx & (t.TC - 1), h = idx >> t.logTC;
     const int k = k0 + c;
@@ -187,7 +304,7 @@ __global__ __launch_bounds__(256) void k_l1fft_cols(float2* __restrict__ spec, i
     const int k = k0 + c;
     if (k < Wh) base[(long)h * Wh + k] = s[fft_slot(h, t) * t.pitch + c];
   }
-  l1fft_block_sum(acc, partials + blockIdx.x);
+  l1fft_block_sum(acc, reinterpret_cast<double*>(tw), partials + blockIdx.x);
 }
 
 // V (the column-inverse of U) is Hermitian along k in every row, so rows A and B of a pair come
@@ -199,7 +316,7 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_inv(const float2* __restrict
                                                         int W, FftTile t, float ga, float gb,
                                                         float* __restrict__ dpred) {
   __shared__ float2 s[kFftLds];
-  __shared__ float2 tw[kFftMaxL / 2];
+  __shared__ float2 tw[kFftMaxL];
   const int Wh = W / 2 + 1;
   const long rp0 = (long)blockIdx.x * t.TC;
   fft_twiddles(tw, W);
@@ -213,15 +330,15 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_inv(const float2* __restrict
       b = spec[(2 * rp + 1) * Wh + k];
     }
     if (k == 0 || k == W / 2) a.y = b.y = 0.f;
-    s[fft_slot(fft_brev(k, t.logL), t) * t.pitch + p] = make_float2(a.x - b.y, a.y + b.x);
+    s[fft_slot(fft_pos(k, t), t) * t.pitch + p] = make_float2(a.x - b.y, a.y + b.x);
     if (k > 0 && k < W / 2)
-      s[fft_slot(fft_brev(W - k, t.logL), t) * t.pitch + p] = make_float2(a.x + b.y, b.x - a.y);
+      s[fft_slot(fft_pos(W - k, t), t) * t.pitch + p] = make_float2(a.x + b.y, b.x - a.y);
   }
   __syncthreads();
   fft_run<true>(s, tw, t);
-  const int n = t.TC << t.logL;
+  const int n = t.TC * t.L;
   for (int idx = threadIdx.x; idx < n; idx += 256) {
-    const int w = idx & (W - 1), p = idx >> t.logL;
+    const int p = idx / W, w = idx - p * W;
     const long rp = rp0 + p;
     if (rp >= R) break;
     const float2 z = s[fft_slot(w, t) * t.pitch + p];
@@ -236,13 +353,14 @@ __global__ __launch_bounds__(256) void k_l1fft_pixel(const float* __restrict__ p
                                                      const float* __restrict__ tgt, long total,
                                                      float ga, float* __restrict__ dpred,
                                                      double* __restrict__ partials) {
+  __shared__ double red[4];
   double acc = 0.0;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const float d = pred[e] - tgt[e];
     acc += fabs((double)d);
     dpred[e] = ga * l1fft_sgn(d);
   }
-  l1fft_block_sum(acc, partials + blockIdx.x);
+  l1fft_block_sum(acc, red, partials + blockIdx.x);
 }
 
 // thread t adds blocks t, t + 256, ... in order, then a fixed tree: sums[0] over the first n0
@@ -275,7 +393,12 @@ __global__ __launch_bounds__(256) void k_l1fft_finalize(const double* __restrict
 
 constexpr int kL1Blocks = 1024;  // the beta == 0 path's fixed grid
 
-bool l1fft_pow2(int v) { return v >= 8 && v <= kFftMaxL && (v & (v - 1)) == 0; }
+// L = m 2^k with m odd, m <= 31, k >= 3, L <= 1024
+bool l1fft_len_ok(int v) {
+  if (v < 8 || v > kFftMaxL || (v & 7) != 0) return false;
+  while ((v & 1) == 0) v >>= 1;
+  return v <= kFftMaxOdd;
+}
 
 struct L1fftPlan {
   FftTile rows, cols;
@@ -285,7 +408,7 @@ struct L1fftPlan {
 };
 
 bool l1fft_plan(int N, int C, int H, int W, L1fftPlan& p) {
-  if (N < 1 || C < 1 || !l1fft_pow2(H) || !l1fft_pow2(W)) return false;
+  if (N < 1 || C < 1 || !l1fft_len_ok(H) || !l1fft_len_ok(W)) return false;
   const long planes = (long)N * C;
   p.rows = fft_tile_for(W, 1);
   p.cols = fft_tile_for(H, 0);

@@ -26,7 +26,7 @@ from . import dist as dp
 from .arch_unet import UNet
 from .n2n import AugmentNoise, _partials_for, n2n_loss, n2n_subsample
 from .optim import FlatAdam, lr_at_epoch
-from .util import l1fft_loss_into, l1fft_supported, structure_loss_into
+from .util import L1FFT_RULE, l1fft_loss_into, l1fft_supported, structure_loss_into
 
 
 class N2NTrainer:
@@ -240,8 +240,9 @@ class SupervisedTrainer:
 
     One forward and one backward of N images (StructureTrainer with weights (1, 0, 0) gives the
     same loss from a 2N batch whose second half gets zero gradient).  net: UNet, RESNET or
-    ImprovedUNet.  'l1fft' needs H and W powers of two in [8, 1024]; alpha and beta are its
-    weights ('l1' is nn.L1Loss and takes neither).
+    ImprovedUNet.  'l1fft' needs H and W of the form m * 2^k with m odd, 1 <= m <= 31, k >= 3,
+    at most 1024 (every multiple of 32 up to 1024: whole 704 x 704 images and 352 tiles as well
+    as power-of-two crops); alpha and beta are its weights ('l1' is nn.L1Loss and takes neither).
     Returns loss3 = [pixel L1, spectrum L1 (0 for 'l1'), total] (device tensor).
     """
 
@@ -277,7 +278,7 @@ class SupervisedTrainer:
         if C != self.net.in_nc or clean.shape != (N, self.net.out_nc, H, W):
             raise ValueError("noisy must be [N, in_nc, H, W] and clean [N, out_nc, H, W]")
         if self.criterion == "l1fft" and not l1fft_supported(H, W):
-            raise ValueError(f"L1FFT needs H and W powers of two in [8, 1024], got {H} x {W}")
+            raise ValueError(f"L1FFT needs {L1FFT_RULE}, got {H} x {W}")
         b = self._buffers(N, H, W, clean.device)
         self.net._run_forward(noisy, b["pred"], b["ws"])
         if self.criterion == "l1fft":

@@ -72,9 +72,19 @@ class Structure_loss(nn.Module):  # noqa: N801  (reference name, util.py:41)
 _l1fft_ws = {}
 
 
+L1FFT_RULE = "H and W of the form m * 2^k with m odd, 1 <= m <= 31, k >= 3, at most 1024"
+
+
 def l1fft_supported(H: int, W: int) -> bool:
-    """the transform lengths dn_l1fft_loss has: powers of two from 8 to 1024"""
-    return all(8 <= v <= 1024 and v & (v - 1) == 0 for v in (int(H), int(W)))
+    """the transform lengths dn_l1fft_loss has, H and W independently: L = m * 2^k with m odd,
+    1 <= m <= 31, k >= 3 and L <= 1024 (every multiple of 32 and every power of two from 8 up
+    to 1024)"""
+    def ok(v: int) -> bool:
+        if v < 8 or v > 1024 or v % 8:
+            return False
+        return v // (v & -v) <= 31  # the odd part
+
+    return ok(int(H)) and ok(int(W))
 
 
 def _l1fft_ws_for(N, C, H, W, device) -> torch.Tensor:
@@ -89,8 +99,9 @@ def _l1fft_ws_for(N, C, H, W, device) -> torch.Tensor:
 
 def l1fft_loss_into(pred, target, alpha, beta, dpred, loss3, reduction="mean"):
     """dn_l1fft_loss into given contiguous buffers: loss3 = [pixel, freq, total],
-    dpred = dL/dpred (all on pred's device and stream).  H and W must be powers of two in
-    [8, 1024]: anything else raises ValueError (there is no other path)."""
+    dpred = dL/dpred (all on pred's device and stream).  H and W must each be m * 2^k with m odd,
+    1 <= m <= 31, k >= 3, and at most 1024 (l1fft_supported): anything else raises ValueError
+    (there is no other path)."""
     if reduction not in ("mean", "sum"):
         raise NotImplementedError("L1FFT supports reduction='mean' and 'sum'")
     for t in (pred, target, dpred, loss3):
@@ -101,7 +112,7 @@ def l1fft_loss_into(pred, target, alpha, beta, dpred, loss3, reduction="mean"):
         raise ValueError("pred, target and dpred must share one [N,C,H,W] shape, loss3 holds 3")
     N, C, H, W = pred.shape
     if N < 1 or C < 1 or not l1fft_supported(H, W):
-        raise ValueError(f"L1FFT needs H and W powers of two in [8, 1024], got {H} x {W}")
+        raise ValueError(f"L1FFT needs {L1FFT_RULE}, got {H} x {W}")
     ws = _l1fft_ws_for(N, C, H, W, pred.device)
     _lib.call("dn_l1fft_loss", _lib.ptr(pred), _lib.ptr(target), N, C, H, W, float(alpha),
               float(beta), int(reduction == "sum"), _lib.ptr(dpred), _lib.ptr(loss3),
@@ -132,7 +143,9 @@ class _L1FFTFn(torch.autograd.Function):
 
 class L1FFT(nn.Module):  # reference name, util.py:5
     """alpha * L1(pred, target) + beta * |fft2(pred) - fft2(target)| reduced like the L1 term.
-    The gradient flows to pred only (the target is data), as for the other losses here."""
+    The gradient flows to pred only (the target is data), as for the other losses here.
+    H and W: m * 2^k with m odd, 1 <= m <= 31, k >= 3, at most 1024 (every multiple of 32 up to
+    1024, so 96, 352 or 704 as well as the powers of two); ValueError otherwise."""
 
     def __init__(self, alpha: float = 1.0, beta: float = 1.0, reduction: str = "mean"):
         super().__init__()

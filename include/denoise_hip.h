@@ -249,8 +249,9 @@ dn_status dn_structure_loss(const float* pred, const float* pred2, const float* 
                             float* dpred2, float* loss5, void* partial_ws, void* stream);
 /* L1FFT, util.py:5-38: L = alpha*L1(pred,tgt) + beta*mean|fft2(pred) - fft2(tgt)| (fft2 over the
    last two dimensions, unnormalised, mean over the full H x W spectrum of every plane;
-   reduction_sum != 0: both means become sums).  H and W must be powers of two in [8, 1024]
-   (anything else: DN_ERR_ARG, there is no other path).  Writes dpred = dL/dpred (spectrum bins of
+   reduction_sum != 0: both means become sums).  H and W must each be m * 2^k with m odd,
+   1 <= m <= 31, k >= 3, and at most 1024: every multiple of 32 and every power of two from 8 up
+   to 1024 (anything else: DN_ERR_ARG, there is no other path).  Writes dpred = dL/dpred (spectrum bins of
    magnitude 0 contribute no gradient, as torch's complex abs) and loss3 = {pixel, freq, total}
    (device floats).  beta == 0 runs no transform.  ws: 16-byte aligned, dn_l1fft_ws_size() bytes
    (0 for an unsupported shape); a smaller ws_bytes is DN_ERR_WORKSPACE. */

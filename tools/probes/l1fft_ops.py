@@ -1,7 +1,11 @@
 """Probe of the L1FFT loss (csrc/fft_loss.hip) and the supervised step.  Its output is
-profiles/l1fft_ops.txt.
+profiles/l1fft_ops.txt (--mixed: profiles/l1fft_mixed_ops.txt).
 
     python tools/probes/l1fft_ops.py [out.txt]
+    python tools/probes/l1fft_ops.py --mixed [out.txt]     -> profiles/l1fft_mixed_ops.txt
+
+--mixed runs part (i) and (ii) alone at the mixed-radix sizes 4 x 1 x 704^2 (whole images, the
+batch of the reference's default log name) and 16 x 1 x 352^2 (the evaluation tiles).
 
 (i)   dn_l1fft_loss at 64 x 1 x 256^2 and 16 x 1 x 512^2 against the same loss and gradient
       through torch.fft autograd on the same GPU, and dn_structure_loss at the same sizes as
@@ -62,10 +66,12 @@ def torch_l1fft(pred, target):
 
 
 def main():
+    args = [a for a in sys.argv[1:] if a != "--mixed"]
+    mixed = "--mixed" in sys.argv[1:]
     g = torch.Generator().manual_seed(0)
     say(f"# {torch.cuda.get_device_name(0)}; {_lib.lib().dn_version().decode()}")
     say("# (i) loss + gradient, ms per call, 5 rounds of 20 calls (HIP events)")
-    for N, HW in ((64, 256), (16, 512)):
+    for N, HW in ((4, 704), (16, 352)) if mixed else ((64, 256), (16, 512)):
         pred = torch.rand(N, 1, HW, HW, generator=g).to(DEV)
         tgt = torch.rand(N, 1, HW, HW, generator=g).to(DEV)
         dp, dp2 = torch.empty_like(pred), torch.empty_like(pred)
@@ -93,6 +99,8 @@ def main():
         del pred, tgt, dp, dp2, gt
         torch.cuda.empty_cache()
 
+    if mixed:
+        return write(args, "l1fft_mixed_ops.txt")
     say("# (iii) training step at 64 x 1 x 256^2, UNet(48), ms per step")
     clean = torch.rand(64, 1, 256, 256, generator=g).to(DEV)
     noisy = (clean + 0.1 * torch.randn(64, 1, 256, 256, generator=g).to(DEV)).clamp(0, 1)
@@ -104,7 +112,11 @@ def main():
         say(f"  {name}: {fmt(timed(lambda: tr.train_step(clean, noisy), calls=5, rounds=5, warm=3))} ms")
         del tr
         torch.cuda.empty_cache()
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "l1fft_ops.txt")
+    write(args, "l1fft_ops.txt")
+
+
+def write(args, default):
+    out = args[0] if args else os.path.join(ROOT, "profiles", default)
     with open(out, "w") as f:
         f.write("\n".join(LINES) + "\n")
 
