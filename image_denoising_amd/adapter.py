@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat_module import FlatParamModule
 
 
 def adapter_reference_init(in_channels: int, hidden_channels: int = 16) -> torch.Tensor:
@@ -23,10 +24,6 @@ def adapter_reference_init(in_channels: int, hidden_channels: int = 16) -> torch
         c1 = nn.Conv2d(2 * in_channels, hidden_channels, kernel_size=3, padding=1, bias=True)
         c2 = nn.Conv2d(hidden_channels, in_channels, kernel_size=3, padding=1, bias=True)
         return torch.cat([c1.weight.reshape(-1), c1.bias, c2.weight.reshape(-1), c2.bias]).float()
-
-
-class _Holder(nn.Module):
-    pass
 
 
 class _AdapterFunction(torch.autograd.Function):
@@ -44,13 +41,14 @@ class _AdapterFunction(torch.autograd.Function):
         mod = ctx.mod
         dflat = torch.empty_like(mod._flat)
         mod._run_backward(noisy, base_out, dout.contiguous(), dflat)
-        grads = [dflat[o:o + n].view(shape) for (o, n, shape) in mod._views]
-        return (None, None, None, *grads)
+        return (None, None, None, *mod._grads_from_flat(dflat, ctx.needs_input_grad[3:]))
 
 
-class OutputAdapter(nn.Module):
+class OutputAdapter(FlatParamModule):
     """adapter.py:5 OutputAdapter(in_channels=1, hidden_channels=16):
     out = base_out + net(cat[noisy, base_out]), net = Conv3x3(2C,16) -> ReLU -> Conv3x3(16,C)."""
+
+    _display = "adapter"
 
     def __init__(self, in_channels: int = 1, hidden_channels: int = 16):
         super().__init__()
@@ -60,42 +58,14 @@ class OutputAdapter(nn.Module):
         self.in_channels, self.hidden_channels = in_channels, hidden_channels
         flat = adapter_reference_init(in_channels, hidden_channels)
         assert flat.numel() == n.value
-        self._flat = flat
         C, Hd = in_channels, hidden_channels
-        self.net = _Holder()
-        shapes = [("0", "weight", (Hd, 2 * C, 3, 3)), ("0", "bias", (Hd,)),
-                  ("2", "weight", (C, Hd, 3, 3)), ("2", "bias", (C,))]
-        self._views, self._layout = [], []
-        off = 0
-        for mod, attr, shape in shapes:
-            if not hasattr(self.net, mod):
-                self.net.add_module(mod, _Holder())
-            cnt = int(torch.Size(shape).numel())
-            setattr(getattr(self.net, mod), attr, nn.Parameter(flat[off:off + cnt].view(shape)))
-            self._views.append((off, cnt, shape))
-            self._layout.append((getattr(self.net, mod), attr, off, cnt, shape))
-            off += cnt
+        self._bind_flat(flat, [("net.0.weight", (Hd, 2 * C, 3, 3)), ("net.0.bias", (Hd,)),
+                               ("net.2.weight", (C, Hd, 3, 3)), ("net.2.bias", (C,))])
         self.net.add_module("1", nn.ReLU(inplace=True))  # adapter.py:17 (no parameters)
         self._slab = None
 
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat
-
-    def _apply(self, fn, recurse=True):  # keep the parameters views of ONE flat buffer
-        new = fn(self._flat)
-        if not isinstance(new, torch.Tensor) or new.dtype != torch.float32:
-            raise ValueError("adapter parameters are fp32")
-        self._flat = new.contiguous()
-        for (h, a, off, cnt, shape) in self._layout:
-            p = getattr(h, a)
-            p.data = self._flat[off:off + cnt].view(shape)
-            p.grad = None
+    def _drop_scratch(self) -> None:
         self._slab = None
-        return self
-
-    def _params(self):
-        return [getattr(h, a) for (h, a, *_ ) in self._layout]
 
     def _check(self, noisy, base_out):
         if noisy.device.type != "cuda":

@@ -4,7 +4,9 @@ Same constructor signature, same `state_dict` keys/shapes (so reference checkpoi
 `load_state_dict`), same `forward(x[N,C,H,W]) -> [N,out_nc,H,W]`.  Internally all parameters are
 views into ONE flat fp32 buffer in state_dict order (the layout the C-ABI consumes), and the
 forward/backward run through dn_unet_forward / dn_unet_backward (parameter gradients and, when the
-input requires grad, dL/dx).  The blind-spot variant
+input requires grad, dL/dx).  That machinery is flat_module.HipNet's, shared with RESNET and
+ImprovedUNet; this file holds the UNet's own: layer table, init replay, bf16 inference,
+prepacked weights, the N2N pair-pixel pass and the split backward.  The blind-spot variant
 (arch_unet.py:65-97) is out of scope and raises.
 """
 from __future__ import annotations
@@ -16,6 +18,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from . import _lib
+from .flat_module import HipNet
 
 # state_dict order of arch_unet.py:115-192
 LAYER_NAMES = [
@@ -53,6 +56,12 @@ def layer_shapes(in_nc: int, out_nc: int, nf: int):
 
 def param_count(in_nc: int, out_nc: int, nf: int) -> int:
     return sum(int(torch.Size(w).numel()) + b for _, w, b, _ in layer_shapes(in_nc, out_nc, nf))
+
+
+def flat_entries(shapes):
+    """layer_shapes() rows as the [(dotted parameter name, shape)] list the flat buffer is bound by"""
+    return [e for name, wshape, blen, _ in shapes
+            for e in ((name + ".weight", wshape), (name + ".bias", (blen,)))]
 
 
 def _kaiming01(m: nn.Module) -> None:
@@ -118,137 +127,20 @@ def reference_init(in_nc: int, out_nc: int, nf: int = 48, zero_last: bool = Fals
         return torch.cat(parts).float().contiguous()
 
 
-class _Holder(nn.Module):
-    """Parameter container so that state_dict keys read e.g. 'enc_conv0.weight'."""
-
-
-class _UNetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        N, C, H, W = x.shape
-        y = torch.empty((N, net.out_nc, H, W), dtype=torch.float32, device=x.device)
-        ws = net._workspace(N, H, W, with_backward=True, fresh=True)
-        net._run_forward(x, y, ws)
-        ctx.net = net
-        ctx.ws = ws
-        ctx.shape = (N, H, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        N, H, W = ctx.shape
-        dy = dy.contiguous()
-        dflat = torch.empty_like(net._flat)
-        dx = None
-        if ctx.needs_input_grad[0]:  # dL/dx from the same backward pass (dn_unet_backward dx)
-            dx = torch.empty((N, net.in_nc, H, W), dtype=torch.float32, device=dy.device)
-        net._run_backward(dy, dflat, ctx.ws, N, H, W, dx=dx)
-        ctx.ws = None
-        grads = [dflat[o:o + p.numel()].view_as(p) if need else None
-                 for (o, p), need in zip(net._param_views(), ctx.needs_input_grad[2:])]
-        return (dx, None, *grads)
-
-
-class UNet(nn.Module):
+class UNet(HipNet):
     """arch_unet.py:100 UNet(in_nc=3, out_nc=3, n_feature=48, blindspot=False, zero_last=False)."""
 
+    _family, _display = "unet", "UNet"
+    _multiple, _multiple_why = 32, "arch_unet.py: 5 pooling levels"
+    _has_split_backward = True
+
     def __init__(self, in_nc=3, out_nc=3, n_feature=48, blindspot=False, zero_last=False):
-        super().__init__()
         if blindspot:
             raise NotImplementedError("blind-spot UNet (arch_unet.py:65-97) is out of scope")
-        self.in_nc, self.out_nc, self.n_feature = in_nc, out_nc, n_feature
+        super().__init__(in_nc, out_nc, n_feature)
         self.blindspot, self.zero_last = blindspot, zero_last
-        self._cfg = _lib.cfg(in_nc, out_nc, n_feature)
-        n = ctypes.c_size_t()
-        _lib.check(_lib.lib().dn_unet_param_count(ctypes.byref(self._cfg), ctypes.byref(n)),
-                   "dn_unet_param_count")
-        flat = reference_init(in_nc, out_nc, n_feature, zero_last)
-        assert flat.numel() == n.value, (flat.numel(), n.value)
-        self._flat = flat
-        self._layout = []  # (holder, attr, offset, shape)
-        off = 0
-        for name, wshape, blen, _ in layer_shapes(in_nc, out_nc, n_feature):
-            holder = self
-            parts = name.split(".")
-            for p in parts:
-                if not hasattr(holder, p) or not isinstance(getattr(holder, p), nn.Module):
-                    setattr(holder, p, _Holder())
-                holder = getattr(holder, p)
-            wn = int(torch.Size(wshape).numel())
-            holder.weight = nn.Parameter(flat[off:off + wn].view(wshape))
-            self._layout.append((holder, "weight", off, wshape))
-            off += wn
-            holder.bias = nn.Parameter(flat[off:off + blen])
-            self._layout.append((holder, "bias", off, (blen,)))
-            off += blen
-        self._ws_cache = {}
-
-    # ---- flat-buffer plumbing -------------------------------------------------------
-    @property
-    def flat_params(self) -> torch.Tensor:
-        """the flat fp32 parameter buffer every parameter is a view of"""
-        return self._flat
-
-    def _param_views(self):
-        return [(off, getattr(h, a)) for (h, a, off, _) in self._layout]
-
-    def _apply(self, fn, recurse=True):  # keep the parameters views of ONE flat buffer
-        new = fn(self._flat)
-        if not isinstance(new, torch.Tensor) or new.dtype != torch.float32:
-            raise ValueError("UNet parameters are fp32 (the HIP path computes in fp32)")
-        self._flat = new.contiguous()
-        for (h, a, off, shape) in self._layout:
-            p = getattr(h, a)
-            n = int(torch.Size(shape).numel())
-            p.data = self._flat[off:off + n].view(shape)
-            p.grad = None
-        self._ws_cache = {}
-        return self
-
-    def _workspace(self, N, H, W, with_backward, fresh=False):
-        key = (N, H, W, bool(with_backward), self._flat.device)
-        if not fresh and key in self._ws_cache:
-            return self._ws_cache[key]
-        nbytes = ctypes.c_size_t()
-        _lib.check(_lib.lib().dn_unet_workspace_size(ctypes.byref(self._cfg), N, H, W,
-                                                     int(with_backward), ctypes.byref(nbytes)),
-                   "dn_unet_workspace_size")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self._flat.device)
-        if not fresh:
-            self._ws_cache = {key: ws}
-        return ws
-
-    def _check_input(self, x):
-        if x.device.type != "cuda":
-            raise RuntimeError("the HIP UNet runs on a GPU: move the module and input to cuda")
-        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != self.in_nc:
-            raise ValueError(f"expected float32 [N,{self.in_nc},H,W], got {x.dtype} {tuple(x.shape)}")
-        if self._flat.device != x.device:
-            raise RuntimeError("module parameters and input are on different devices")
-
-    # arithmetic of the 3x3 convolutions (include/denoise_hip.h DN_PREC_*)
-    _PRECISIONS = {"fp32": 0, "fp32_x6": 2}
-
-    def set_precision(self, mode: str) -> "UNet":
-        """Arithmetic of the 3x3 convolutions in training and fp32 inference:
-        'fp32'    fp32 operands on the fp32 matrix cores (v_mfma_f32_16x16x4_f32);
-        'fp32_x6' fp32 operands split exactly into three bf16 pieces, the six piece products
-                  of order <= 2 on the bf16 matrix cores, fp32 accumulation -- the rounding
-                  error of an fp32 dot product at 2.67x the matrix-core peak."""
-        if mode not in self._PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(self._PRECISIONS)}")
-        self.precision = mode
-        return self
-
-    def _prec(self) -> int:
-        return self._PRECISIONS[getattr(self, "precision", "fp32")]
-
-    def _run_forward(self, x, y, ws):
-        N, _, H, W = x.shape
-        _lib.call("dn_unet_forward_prec", ctypes.byref(self._cfg), _lib.ptr(self._flat),
-                  _lib.ptr(x), _lib.ptr(y), N, H, W, ws.data_ptr(), ws.numel(), self._prec(),
-                  _lib.stream_of(x))
+        self._bind_net(reference_init(in_nc, out_nc, n_feature, zero_last),
+                       flat_entries(layer_shapes(in_nc, out_nc, n_feature)))
 
     def _infer_prec(self) -> int:
         """the precision code of a no-grad forward (bf16 for the configs[4] frozen base)"""
@@ -292,12 +184,6 @@ class UNet(nn.Module):
         _lib.call("dn_unet_forward_bf16", ctypes.byref(self._cfg), _lib.ptr(self._flat),
                   _lib.ptr(x), _lib.ptr(y), N, H, W, ws.data_ptr(), ws.numel(), _lib.stream_of(x))
 
-    def _run_backward(self, dy, dflat, ws, N, H, W, dx=None):
-        """dflat = dL/dparams (and dx = dL/dx when given) for dy = dL/dy"""
-        _lib.call("dn_unet_backward_prec", ctypes.byref(self._cfg), _lib.ptr(self._flat),
-                  _lib.ptr(dy), _lib.ptr(dflat), _lib.ptr(dx), N, H, W, ws.data_ptr(), ws.numel(),
-                  self._prec(), _lib.stream_of(dy))
-
     def _run_backward_split(self, dy, dflat, ws, N, H, W, tail_ready):
         """_run_backward that records tail_ready (a torch.cuda.Event) once dflat[tail_begin():]
         is final, while the encoder's gradients are still being computed
@@ -313,18 +199,3 @@ class UNet(nn.Module):
         _lib.call("dn_unet_backward_split", ctypes.byref(self._cfg), None, None, None, None, 1, 32,
                   32, None, 0, self._prec(), None, None, ctypes.byref(t))
         return int(t.value)
-
-    # ---- nn.Module API ----------------------------------------------------------------
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x.contiguous()
-        self._check_input(x)
-        N, _, H, W = x.shape
-        if H % 32 or W % 32:
-            raise ValueError("H and W must be multiples of 32 (arch_unet.py: 5 pooling levels)")
-        if torch.is_grad_enabled() and (x.requires_grad or
-                                        any(p.requires_grad for p in self.parameters())):
-            # autograd: parameter gradients and/or dL/dx, as the reference module gives
-            return _UNetFunction.apply(x, self, *[p for _, p in self._param_views()])
-        y = torch.empty((N, self.out_nc, H, W), dtype=torch.float32, device=x.device)
-        self._run_forward_inference(x, y, self._workspace(N, H, W, with_backward=False))
-        return y

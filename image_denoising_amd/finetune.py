@@ -22,12 +22,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from . import dist as dp
 from .adapter import DenoiserWithAdapter
 from .arch_unet import UNet
 from .checkpoint import strip_module_prefix
+from .flat_module import HipNet
 from .n2n import _partials_for
-from .optim import FlatAdam
+from .trainer import _FlatStepBase
 
 
 def gradient(x: torch.Tensor):
@@ -224,7 +224,7 @@ def load_base_weights(model: nn.Module, ckpt_path: str):
     return model.load_state_dict(state, strict=False)
 
 
-class _AdapterStepBase:
+class _AdapterStepBase(_FlatStepBase):
     """What the adapter finetune steps share: the loss settings, the replicas' broadcast, Adam over
     the adapter's flat buffer, the step's buffers and the workspace-reusing frozen-base call."""
 
@@ -242,16 +242,11 @@ class _AdapterStepBase:
             if unknown:
                 raise ValueError(f"unknown IQSL settings: {sorted(unknown)}")
             self.iqsl = dict(iqsl)
-        self.distributed = dp.require_group(distributed)
-        ad = model.adapter
-        if self.distributed:  # identical replicas, as nn.DataParallel's per-forward broadcast
-            base_flat = getattr(model.base, "flat_params", None)
-            if base_flat is not None:  # the frozen base (loaded per rank from one checkpoint)
-                dp.broadcast_params(base_flat.data)
-            dp.broadcast_params(ad.flat_params)
-        self.opt = FlatAdam(ad.flat_params, lr=lr)
-        self.grad = torch.zeros_like(ad.flat_params)
-        self._bufs = {}
+        # identical replicas, as nn.DataParallel's per-forward broadcast: the adapter, and the
+        # frozen base when it is one of ours (loaded per rank from one checkpoint)
+        base = model.base
+        self._init_step(model.adapter.flat_params, lr, distributed,
+                        frozen=base.flat_params.data if isinstance(base, HipNet) else None)
 
     def _buffers(self, shape, device):
         key = (tuple(shape), device)
@@ -262,10 +257,9 @@ class _AdapterStepBase:
 
     def _base_forward(self, noisy, out):
         base = self.model.base
-        if hasattr(base, "_run_forward"):  # HIP base: workspace reused across steps
+        if isinstance(base, HipNet):  # workspace reused across steps; UNet: bf16 if set
             N, _, H, W = noisy.shape
-            run = getattr(base, "_run_forward_inference", base._run_forward)  # bf16 if set
-            run(noisy, out, base._workspace(N, H, W, with_backward=False))
+            base._run_forward_inference(noisy, out, base._workspace(N, H, W, with_backward=False))
         else:
             with torch.no_grad():
                 out.copy_(base(noisy))
@@ -275,10 +269,6 @@ class _AdapterStepBase:
         if self.iqsl is not None:
             return finetune_iqsl_loss(pred, clean, self.lambda_grad, self.lambda_iqsl, **self.iqsl)
         return finetune_loss(pred, clean, self.lambda_grad)
-
-    def _update(self):
-        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
-        self.opt.step(self.grad, grad_scale=scale)
 
 
 class FinetuneTrainer(_AdapterStepBase):

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat_module import FlatParamModule
 
 
 class MemoryBank:
@@ -155,10 +156,6 @@ def memadapter_reference_init(in_channels: int, hidden_channels: int, num_fft_bi
                           for t in (m.weight, m.bias)]).float()
 
 
-class _Holder(nn.Module):
-    pass
-
-
 class _MemAdapterFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, noisy, base_out, mem_clean, mod, *params):
@@ -174,16 +171,17 @@ class _MemAdapterFunction(torch.autograd.Function):
         mod = ctx.mod
         dflat = torch.empty_like(mod._flat)
         mod._run_backward(noisy, base_out, feat, dout.contiguous(), dflat)
-        grads = [dflat[o:o + n].view(shape) for (o, n, shape) in mod._views]
-        return (None, None, None, None, *grads)
+        return (None, None, None, None, *mod._grads_from_flat(dflat, ctx.needs_input_grad[4:]))
 
 
-class HyperGatedResidualAdapter_FFT(nn.Module):
+class HyperGatedResidualAdapter_FFT(FlatParamModule):
     """finetune_memory.py HyperGatedResidualAdapter_FFT (the "v5" adapter):
     out = clamp(base_out + gamma * local_net(cat[noisy, base_out]) + beta), (gamma, beta) from a
     small MLP of global statistics and row-FFT band features of noisy, base_out and mem_clean.
     Same state_dict keys (`local_net.{0,2,4}`, `hyper_mlp.{0,2}`); all parameters are views of one
     flat fp32 buffer."""
+
+    _display = "adapter"
 
     def __init__(self, in_channels: int = 1, hidden_channels: int = 16, num_fft_bins: int = 3,
                  clamp_output: bool = True):
@@ -196,43 +194,16 @@ class HyperGatedResidualAdapter_FFT(nn.Module):
         self.beta_scale = 0.1
         flat = memadapter_reference_init(in_channels, hidden_channels, num_fft_bins)
         assert flat.numel() == n.value
-        self._flat = flat
         C, Hc, NF = in_channels, hidden_channels, 6 + 3 * num_fft_bins
-        self.local_net, self.hyper_mlp = _Holder(), _Holder()
-        shapes = [(self.local_net, "0", (Hc, 2 * C, 3, 3)), (self.local_net, "2", (Hc, Hc, 3, 3)),
-                  (self.local_net, "4", (C, Hc, 3, 3)), (self.hyper_mlp, "0", (Hc, NF)),
-                  (self.hyper_mlp, "2", (2 * C, Hc))]
-        self._views, self._layout = [], []
-        off = 0
-        for parent, name, wshape in shapes:
-            h = _Holder()
-            parent.add_module(name, h)
-            for attr, shape in (("weight", wshape), ("bias", (wshape[0],))):
-                cnt = int(torch.Size(shape).numel())
-                setattr(h, attr, nn.Parameter(flat[off:off + cnt].view(shape)))
-                self._views.append((off, cnt, shape))
-                self._layout.append((h, attr, off, cnt, shape))
-                off += cnt
+        layers = [("local_net.0", (Hc, 2 * C, 3, 3)), ("local_net.2", (Hc, Hc, 3, 3)),
+                  ("local_net.4", (C, Hc, 3, 3)), ("hyper_mlp.0", (Hc, NF)),
+                  ("hyper_mlp.2", (2 * C, Hc))]
+        self._bind_flat(flat, [e for name, wshape in layers
+                               for e in ((name + ".weight", wshape), (name + ".bias", wshape[:1]))])
         self._ws = None
 
-    @property
-    def flat_params(self) -> torch.Tensor:
-        return self._flat
-
-    def _apply(self, fn, recurse=True):  # keep the parameters views of ONE flat buffer
-        new = fn(self._flat)
-        if not isinstance(new, torch.Tensor) or new.dtype != torch.float32:
-            raise ValueError("adapter parameters are fp32")
-        self._flat = new.contiguous()
-        for (h, a, off, cnt, shape) in self._layout:
-            p = getattr(h, a)
-            p.data = self._flat[off:off + cnt].view(shape)
-            p.grad = None
+    def _drop_scratch(self) -> None:
         self._ws = None
-        return self
-
-    def _params(self):
-        return [getattr(h, a) for (h, a, *_) in self._layout]
 
     def _check(self, noisy, base_out, mem_clean):
         if noisy.device.type != "cuda":

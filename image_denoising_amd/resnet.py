@@ -12,13 +12,11 @@ The blind-spot variant raises.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .arch_unet import _Holder, _kaiming01
+from .arch_unet import _kaiming01, flat_entries
+from .flat_module import HipNet
 
 # state_dict order of arch_unet.py:279-346
 LAYER_NAMES = [
@@ -96,37 +94,13 @@ def reference_init(in_nc: int, out_nc: int, nf: int = 48, zero_last: bool = Fals
         return torch.cat(parts).float().contiguous()
 
 
-class _ResnetFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, net, *params):
-        N, C, H, W = x.shape
-        y = torch.empty((N, net.out_nc, H, W), dtype=torch.float32, device=x.device)
-        ws = net._workspace(N, H, W, with_backward=True, fresh=True)
-        net._run_forward(x, y, ws)
-        ctx.net, ctx.ws, ctx.shape = net, ws, (N, H, W)
-        return y
+class RESNET(HipNet):
+    """arch_unet.py:263 RESNET(in_nc=3, out_nc=3, n_feature=48, blindspot=False, zero_last=False).
+    Any H, W; the backward leaves zeros over up5.deconv's gradient; bf16 inference is not built."""
 
-    @staticmethod
-    def backward(ctx, dy):
-        net = ctx.net
-        N, H, W = ctx.shape
-        dy = dy.contiguous()
-        dflat = torch.empty_like(net._flat)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, net.in_nc, H, W), dtype=torch.float32, device=dy.device)
-        net._run_backward(dy, dflat, ctx.ws, N, H, W, dx=dx)
-        ctx.ws = None
-        grads = [dflat[o:o + p.numel()].view_as(p) if need else None
-                 for (o, p), need in zip(net._param_views(), ctx.needs_input_grad[2:])]
-        return (dx, None, *grads)
-
-
-class RESNET(nn.Module):
-    """arch_unet.py:263 RESNET(in_nc=3, out_nc=3, n_feature=48, blindspot=False, zero_last=False)."""
+    _family, _display = "resnet", "RESNET"
 
     def __init__(self, in_nc=3, out_nc=3, n_feature=48, blindspot=False, zero_last=False):
-        super().__init__()
         if blindspot:
             raise NotImplementedError("blind-spot RESNET (arch_unet.py:65-97) is out of scope")
         if out_nc != in_nc:
@@ -135,118 +109,7 @@ class RESNET(nn.Module):
         if n_feature != 48:
             raise ValueError("n_feature must be 48 (kernel tiles are instantiated for the "
                              "reference width)")
-        self.in_nc, self.out_nc, self.n_feature = in_nc, out_nc, n_feature
+        super().__init__(in_nc, out_nc, n_feature)
         self.blindspot, self.zero_last = blindspot, zero_last
-        self._cfg = _lib.cfg(in_nc, out_nc, n_feature)
-        n = ctypes.c_size_t()
-        _lib.check(_lib.lib().dn_resnet_param_count(ctypes.byref(self._cfg), ctypes.byref(n)),
-                   "dn_resnet_param_count")
-        flat = reference_init(in_nc, out_nc, n_feature, zero_last)
-        assert flat.numel() == n.value, (flat.numel(), n.value)
-        self._flat = flat
-        self._layout = []  # (holder, attr, offset, shape)
-        off = 0
-        for name, wshape, blen, _ in layer_shapes(in_nc, out_nc, n_feature):
-            holder = self
-            for p in name.split("."):
-                if not hasattr(holder, p) or not isinstance(getattr(holder, p), nn.Module):
-                    setattr(holder, p, _Holder())
-                holder = getattr(holder, p)
-            wn = int(torch.Size(wshape).numel())
-            holder.weight = nn.Parameter(flat[off:off + wn].view(wshape))
-            self._layout.append((holder, "weight", off, wshape))
-            off += wn
-            holder.bias = nn.Parameter(flat[off:off + blen])
-            self._layout.append((holder, "bias", off, (blen,)))
-            off += blen
-        self._ws_cache = {}
-
-    @property
-    def flat_params(self) -> torch.Tensor:
-        """the flat fp32 parameter buffer every parameter is a view of"""
-        return self._flat
-
-    def _param_views(self):
-        return [(off, getattr(h, a)) for (h, a, off, _) in self._layout]
-
-    def param_range(self, name: str):
-        """(begin, end) of layer `name`'s weight and bias in the flat buffer"""
-        off = 0
-        for n, wshape, blen, _ in layer_shapes(self.in_nc, self.out_nc, self.n_feature):
-            cnt = int(torch.Size(wshape).numel()) + blen
-            if n == name:
-                return off, off + cnt
-            off += cnt
-        raise KeyError(name)
-
-    def _apply(self, fn, recurse=True):  # keep the parameters views of ONE flat buffer
-        new = fn(self._flat)
-        if not isinstance(new, torch.Tensor) or new.dtype != torch.float32:
-            raise ValueError("RESNET parameters are fp32 (the HIP path computes in fp32)")
-        self._flat = new.contiguous()
-        for (h, a, off, shape) in self._layout:
-            p = getattr(h, a)
-            p.data = self._flat[off:off + int(torch.Size(shape).numel())].view(shape)
-            p.grad = None
-        self._ws_cache = {}
-        return self
-
-    def _workspace(self, N, H, W, with_backward, fresh=False):
-        key = (N, H, W, bool(with_backward), self._flat.device)
-        if not fresh and key in self._ws_cache:
-            return self._ws_cache[key]
-        nbytes = ctypes.c_size_t()
-        _lib.check(_lib.lib().dn_resnet_workspace_size(ctypes.byref(self._cfg), N, H, W,
-                                                       int(with_backward), ctypes.byref(nbytes)),
-                   "dn_resnet_workspace_size")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self._flat.device)
-        if not fresh:
-            self._ws_cache = {key: ws}
-        return ws
-
-    # arithmetic of the 3x3 convolutions (include/denoise_hip.h DN_PREC_*; bf16 is not built)
-    _PRECISIONS = {"fp32": 0, "fp32_x6": 2}
-
-    def set_precision(self, mode: str) -> "RESNET":
-        """'fp32' (fp32 matrix cores) or 'fp32_x6' (exact three-piece bf16 split, six products,
-        fp32 accumulation)"""
-        if mode not in self._PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(self._PRECISIONS)}")
-        self.precision = mode
-        return self
-
-    def _prec(self) -> int:
-        return self._PRECISIONS[getattr(self, "precision", "fp32")]
-
-    def _run_forward(self, x, y, ws):
-        N, _, H, W = x.shape
-        _lib.call("dn_resnet_forward_prec", ctypes.byref(self._cfg), _lib.ptr(self._flat),
-                  _lib.ptr(x), _lib.ptr(y), N, H, W, ws.data_ptr(), ws.numel(), self._prec(),
-                  _lib.stream_of(x))
-
-    def _run_forward_n2n(self, x, den, ws, rd_idx):
-        """the N2N no-grad pass (N2NTrainer): the whole image, a superset of the rd pair pixels
-        the loss reads (the pair-pixel fast path is built for the UNet)"""
-        self._run_forward(x, den, ws)
-
-    def _run_backward(self, dy, dflat, ws, N, H, W, dx=None):
-        """dflat = dL/dparams (zeros over up5.deconv), and dx = dL/dx when given"""
-        _lib.call("dn_resnet_backward_prec", ctypes.byref(self._cfg), _lib.ptr(self._flat),
-                  _lib.ptr(dy), _lib.ptr(dflat), _lib.ptr(dx), N, H, W, ws.data_ptr(), ws.numel(),
-                  self._prec(), _lib.stream_of(dy))
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x.contiguous()
-        if x.device.type != "cuda":
-            raise RuntimeError("the HIP RESNET runs on a GPU: move the module and input to cuda")
-        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != self.in_nc:
-            raise ValueError(f"expected float32 [N,{self.in_nc},H,W], got {x.dtype} {tuple(x.shape)}")
-        if self._flat.device != x.device:
-            raise RuntimeError("module parameters and input are on different devices")
-        N, _, H, W = x.shape
-        if torch.is_grad_enabled() and (x.requires_grad or
-                                        any(p.requires_grad for p in self.parameters())):
-            return _ResnetFunction.apply(x, self, *[p for _, p in self._param_views()])
-        y = torch.empty((N, self.out_nc, H, W), dtype=torch.float32, device=x.device)
-        self._run_forward(x, y, self._workspace(N, H, W, with_backward=False))
-        return y
+        self._bind_net(reference_init(in_nc, out_nc, n_feature, zero_last),
+                       flat_entries(layer_shapes(in_nc, out_nc, n_feature)))

@@ -29,7 +29,35 @@ from .optim import FlatAdam, lr_at_epoch
 from .util import L1FFT_RULE, l1fft_loss_into, l1fft_supported, structure_loss_into
 
 
-class N2NTrainer:
+class _FlatStepBase:
+    """What every trainer's step shares: the process group, identical replicas, Adam over ONE flat
+    parameter buffer, the flat gradient, the one-entry buffer cache, and the update that ends a
+    step."""
+
+    def _init_step(self, flat: torch.Tensor, lr: float, distributed: bool | None,
+                   frozen: torch.Tensor | None = None) -> None:
+        """`flat`: the trained buffer; `frozen`: parameters that are only made identical"""
+        self.distributed = dp.require_group(distributed)
+        if self.distributed:  # identical replicas: broadcast rank 0's initial weights
+            if frozen is not None:
+                dp.broadcast_params(frozen)
+            dp.broadcast_params(flat)
+        self.opt = FlatAdam(flat, lr=lr)
+        self.grad = torch.zeros_like(flat)
+        self._bufs = {}
+
+    def _adam(self, scale: float, epoch: int | None = None) -> None:
+        """Adam(W, scale * grad), at the schedule's lr of `epoch` when one is given"""
+        if epoch is not None:
+            self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
+        self.opt.step(self.grad, grad_scale=scale)
+
+    def _update(self, epoch: int | None = None) -> None:
+        """one RCCL all-reduce(sum) of the flat gradient (1/world folded into Adam), then Adam"""
+        self._adam(dp.allreduce_grads(self.grad) if self.distributed else 1.0, epoch)
+
+
+class N2NTrainer(_FlatStepBase):
     def __init__(self, net: UNet, lr: float = 3e-4, n_epoch: int = 100,
                  increase_ratio: float = 2.0, gamma: float = 0.5, noise_std: float = 25.0 / 255.0,
                  seed: int = 0, distributed: bool | None = None, noise_style: str | None = None):
@@ -45,18 +73,12 @@ class N2NTrainer:
         self.noise_std = noise_std
         self.noise = AugmentNoise(noise_style) if noise_style else None
         self.seed = seed
-        self.distributed = dp.require_group(distributed)
+        self._init_step(net.flat_params, lr, distributed)
         self.world, self.rank = dp.world_and_rank() if self.distributed else (1, 0)
-        if self.distributed:  # identical replicas: broadcast rank 0's initial weights
-            dp.broadcast_params(net.flat_params)
-        self.opt = FlatAdam(net.flat_params, lr=lr)
-        self.grad = torch.zeros_like(net.flat_params)
         self.global_step = 0
-        self._bufs = {}
         # the overlapped all-reduce needs the split backward (arch_unet.UNet); other nets
-        # (ImprovedUNet) take the one all-reduce after the whole backward
-        self._overlap = (os.environ.get("DN_AR_OVERLAP", "1") != "0"
-                         and hasattr(net, "_run_backward_split") and hasattr(net, "tail_begin"))
+        # (RESNET, ImprovedUNet) take the one all-reduce after the whole backward
+        self._overlap = os.environ.get("DN_AR_OVERLAP", "1") != "0" and net._has_split_backward
         self._tail_begin = net.tail_begin() if self.distributed and self._overlap else 0
 
     @staticmethod
@@ -150,20 +172,18 @@ class N2NTrainer:
         # the decoder + head one overlapping the encoder's backward (DN_AR_OVERLAP=0: one
         # all-reduce after the whole backward)
         if self.distributed and self._overlap:
-            scale = dp.allreduce_grads_split(
+            self._adam(dp.allreduce_grads_split(
                 self.grad, self._tail_begin,
                 lambda ev: self._backward(dout, b["ws_grad"], N, H // 2, W // 2, ev),
-                self._comm_stream(clean.device))
+                self._comm_stream(clean.device)), epoch)
         else:
             self.net._run_backward(dout, self.grad, b["ws_grad"], N, H // 2, W // 2)
-            scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
-        self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
-        self.opt.step(self.grad, grad_scale=scale)
+            self._update(epoch)
         self.global_step += 1
         return loss3
 
 
-class StructureTrainer:
+class StructureTrainer(_FlatStepBase):
     """The step of the reference's own train.py loop (train.py:355-368), fused:
 
         pred, pred2 = UNet([noisy; clean])  [saved]   dn_unet_forward   (train.py:361-362)
@@ -187,12 +207,7 @@ class StructureTrainer:
         self.net = net
         self.base_lr, self.n_epoch, self.gamma = lr, n_epoch, gamma
         self.weights = alpha_beta_gamma
-        self.distributed = dp.require_group(distributed)
-        if self.distributed:
-            dp.broadcast_params(net.flat_params)
-        self.opt = FlatAdam(net.flat_params, lr=lr)
-        self.grad = torch.zeros_like(net.flat_params)
-        self._bufs = {}
+        self._init_step(net.flat_params, lr, distributed)
 
     def _buffers(self, N, C, H, W, device):
         key = (N, C, H, W, device)
@@ -221,13 +236,11 @@ class StructureTrainer:
         pred, pred2 = b["pred"][:N], b["pred"][N:]
         structure_loss_into(pred, pred2, clean, a, be, g, b["dpred"][:N], b["dpred"][N:], b["loss5"])
         self.net._run_backward(b["dpred"], self.grad, b["ws"], 2 * N, H, W)
-        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
-        self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
-        self.opt.step(self.grad, grad_scale=scale)
+        self._update(epoch)
         return b["loss5"].clone()
 
 
-class SupervisedTrainer:
+class SupervisedTrainer(_FlatStepBase):
     """The plain supervised step `criterion(network(noisy), clean)` (train.py:362 with the
     criterion of train.py:318-321; train_opt.py:122-157 without its guards), fused:
 
@@ -254,12 +267,7 @@ class SupervisedTrainer:
         self.net = net
         self.criterion, self.alpha, self.beta = criterion, alpha, beta
         self.base_lr, self.n_epoch, self.gamma = lr, n_epoch, gamma
-        self.distributed = dp.require_group(distributed)
-        if self.distributed:
-            dp.broadcast_params(net.flat_params)
-        self.opt = FlatAdam(net.flat_params, lr=lr)
-        self.grad = torch.zeros_like(net.flat_params)
-        self._bufs = {}
+        self._init_step(net.flat_params, lr, distributed)
 
     def _buffers(self, N, H, W, device):
         key = (N, H, W, device)
@@ -289,7 +297,5 @@ class SupervisedTrainer:
                       _partials_for(clean.device).data_ptr(), _lib.stream_of(clean))
             b["loss3"][1].zero_()  # the unweighted gradient-L1 the kernel also reports
         self.net._run_backward(b["dpred"], self.grad, b["ws"], N, H, W)
-        scale = dp.allreduce_grads(self.grad) if self.distributed else 1.0
-        self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
-        self.opt.step(self.grad, grad_scale=scale)
+        self._update(epoch)
         return b["loss3"].clone()
