@@ -13,11 +13,12 @@
 //
 // The loss kernel fuses L1(pred, clean) + lambda * gradient_loss(pred, clean)
 // (finetune.py:153-162) with its gradient in gather form (no atomics).
+#include "block_reduce.h"
 #include "dn_internal.h"
 
 namespace dn {
 
-constexpr int AD_T = 16;    // output tile edge
+constexpr int AD_T = 16;   // output tile edge
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int AD_HID = 16;  // hidden channels (adapter.py:13 default, finetune.py --adapter_hidden)
@@ -264,13 +265,58 @@ __global__ __launch_bounds__(256, 3) void k_adapter_bwd(const float* __restrict_
 }
 
 // ---- finetune loss (finetune.py:153-162, :283-285) ---------------------------------------
-constexpr int kFtBlocks = 1024;
+// The element counts of the L1 term and of the two gradient terms, and the gradient's scales:
+// d/dp of mean|.| = sgn / numel; the gradient_loss terms carry lambda_grad (finetune.py:285)
+struct FtScale {
+  double M, Mx, My;
+  float g0, gx, gy;
+};
 
-__device__ __forceinline__ float sgn1(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+static FtScale ft_scale(int N, int C, int H, int W, float lam) {
+  FtScale f;
+  f.M = (double)N * C * H * W;
+  f.Mx = (double)N * C * H * (W - 1);
+  f.My = (double)N * C * (H - 1) * W;
+  f.g0 = 1.0f / (float)f.M;
+  f.gx = lam / (float)f.Mx;
+  f.gy = lam / (float)f.My;
+  return f;
+}
 
-__device__ __forceinline__ double wsum64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+// Element e of the finetune loss: v[0..2] += its L1 term and its two gradient-L1 terms,
+// returns d loss / d p[e] in gather form (the element looks at both neighbours, no atomics).
+// k_ft_loss and k_iqsl_sums<true> share it, so their bits are equal.
+template <int T>
+__device__ __forceinline__ float ft_pixel(long e, const float* __restrict__ p,
+                                          const float* __restrict__ t, int H, int W, float g0,
+                                          float gx, float gy, double (&v)[T]) {
+  const int x = (int)(e % W);
+  const int y = (int)((e / W) % H);
+  const float pe = p[e], te = t[e];
+  const float d0 = pe - te;
+  v[0] += fabs((double)d0);
+  float g = g0 * sgn(d0);
+  // gradient(x) = (x[..., 1:] - x[..., :-1], x[:, :, 1:] - x[:, :, :-1])  (finetune.py:153-156)
+  if (x + 1 < W) {
+    const float a = (p[e + 1] - pe) - (t[e + 1] - te);
+    v[1] += fabs((double)a);
+    g -= gx * sgn(a);
+  }
+  if (x > 0) g += gx * sgn((pe - p[e - 1]) - (te - t[e - 1]));
+  if (y + 1 < H) {
+    const float b = (p[e + W] - pe) - (t[e + W] - te);
+    v[2] += fabs((double)b);
+    g -= gy * sgn(b);
+  }
+  if (y > 0) g += gy * sgn((pe - p[e - W]) - (te - t[e - W]));
+  return g;
+}
+
+// [loss_l1, loss_grad] from the three sums
+__device__ __forceinline__ void ft_losses(const double* s, double M, double Mx, double My,
+                                          float& l1, float& lg) {
+  l1 = (float)(s[0] / M);
+  lg = (float)(s[1] / Mx) + (float)(s[2] / My);
 }
 
 __global__ __launch_bounds__(256) void k_ft_loss(const float* __restrict__ p,
@@ -280,63 +326,20 @@ __global__ __launch_bounds__(256) void k_ft_loss(const float* __restrict__ p,
                                                  double* __restrict__ partials) {
   const long total = (long)N * C * H * W;
   double v[3] = {0.0, 0.0, 0.0};
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const int x = (int)(e % W);
-    const int y = (int)((e / W) % H);
-    const float pe = p[e], te = t[e];
-    const float d0 = pe - te;
-    v[0] += fabs((double)d0);
-    float g = g0 * sgn1(d0);
-    // gradient(x) = (x[..., 1:] - x[..., :-1], x[:, :, 1:] - x[:, :, :-1])  (finetune.py:153-156)
-    if (x + 1 < W) {
-      const float a = (p[e + 1] - pe) - (t[e + 1] - te);
-      v[1] += fabs((double)a);
-      g -= gx * sgn1(a);
-    }
-    if (x > 0) g += gx * sgn1((pe - p[e - 1]) - (te - t[e - 1]));
-    if (y + 1 < H) {
-      const float b = (p[e + W] - pe) - (t[e + W] - te);
-      v[2] += fabs((double)b);
-      g -= gy * sgn1(b);
-    }
-    if (y > 0) g += gy * sgn1((pe - p[e - W]) - (te - t[e - W]));
-    dp[e] = g;
-  }
-  __shared__ double red[4][3];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = wsum64(v[k]);
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) red[wv][k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-      partials[blockIdx.x * 4 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256)
+    dp[e] = ft_pixel(e, p, t, H, W, g0, gx, gy, v);
+  static_assert(3 <= kLossStride, "terms exceed the partials stride");
+  block_sum_store(v, partials + blockIdx.x * kLossStride);
 }
 
 __global__ __launch_bounds__(256) void k_ft_finalize(const double* __restrict__ partials, int nblk,
                                                      double M, double Mx, double My, float lam,
                                                      float* __restrict__ loss3) {
-  __shared__ double sh[3][256];
-  const int t = threadIdx.x;
-  double v[3] = {0.0, 0.0, 0.0};
-  for (int b = t; b < nblk; b += 256)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] += partials[b * 4 + k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) sh[k][t] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) sh[k][t] += sh[k][t + w];
-    __syncthreads();
-  }
-  if (t != 0) return;
-  const float l1 = (float)(sh[0][0] / M);
-  const float lg = (float)(sh[1][0] / Mx) + (float)(sh[2][0] / My);
+  double s[3];
+  sum_partials(partials, nblk, kLossStride, s);
+  if (threadIdx.x != 0) return;
+  float l1, lg;
+  ft_losses(s, M, Mx, My, l1, lg);
   loss3[0] = l1;
   loss3[1] = lg;
   loss3[2] = l1 + lam * lg;
@@ -346,9 +349,9 @@ __global__ __launch_bounds__(256) void k_ft_finalize(const double* __restrict__ 
 // loss = L1 + lambda_grad * gradient_loss + lambda_iqsl * iqsl, iqsl = L_dice + ce_factor * ce of
 // a 3-class (dark / mid / bright) soft segmentation of the prediction against the thresholded
 // target.  iqsl's gradient at a pixel depends on sums over the whole batch, so:
-//   k_iqsl_sums      one pass: the L1 / gradient-L1 sums and their gradient exactly as k_ft_loss
-//                    forms them (same bits), plus the eleven IQSL sums, per block in fp64
-//   k_iqsl_finalize  fixed-order sum of the block partials -> loss4 and the coefficients
+//   k_iqsl_sums      one pass: the L1 / gradient-L1 sums and their gradient by k_ft_loss's
+//                    ft_pixel (same bits), plus the eleven IQSL sums, per block in fp64
+//   k_iqsl_finalize  the sum of the block partials -> loss4 and the coefficients
 //                    D_k, 2 I_k + eps, 3 V + eps, left behind the partials
 //   k_iqsl_grad      second pass: dpred += lambda_iqsl * d iqsl / d pred
 // Thresholds and centres arrive rounded to fp32 (torch compares an fp32 tensor with a Python
@@ -356,10 +359,11 @@ __global__ __launch_bounds__(256) void k_ft_finalize(const double* __restrict__ 
 // fp32, everything after that fp64.
 constexpr int kIqTerms = 16;  // slots per block: 0-2 L1 | 3-5 I_k | 6-8 P_k | 9-11 T_k | 12 S | 13 V
 constexpr int kIqUsed = 14;
+static_assert(kIqUsed <= kIqTerms, "terms exceed the IQSL partials stride");
 constexpr int kIqCoefs = 8;   // D_0..2, (2 I_k + eps)_0..2, 3 V + eps, iqsl
 constexpr double kIqEps = 1e-6;
 
-size_t iqsl_partials_bytes() { return sizeof(double) * (kFtBlocks * kIqTerms + kIqCoefs); }
+size_t iqsl_partials_bytes() { return sizeof(double) * (kLossBlocks * kIqTerms + kIqCoefs); }
 
 // the pixel's valid flag and class (-1: a NaN target belongs to none) from the fp32 target
 __device__ __forceinline__ bool iq_valid(const IqslScalars& a, float y) {
@@ -401,26 +405,7 @@ __global__ __launch_bounds__(256) void k_iqsl_sums(const float* __restrict__ p,
   for (int k = 0; k < kIqUsed; ++k) v[k] = 0.0;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const float pe = p[e], te = t[e];
-    if (L1) {  // k_ft_loss's body, term for term
-      const int x = (int)(e % W);
-      const int y = (int)((e / W) % H);
-      const float d0 = pe - te;
-      v[0] += fabs((double)d0);
-      float g = g0 * sgn1(d0);
-      if (x + 1 < W) {
-        const float b = (p[e + 1] - pe) - (t[e + 1] - te);
-        v[1] += fabs((double)b);
-        g -= gx * sgn1(b);
-      }
-      if (x > 0) g += gx * sgn1((pe - p[e - 1]) - (te - t[e - 1]));
-      if (y + 1 < H) {
-        const float b = (p[e + W] - pe) - (t[e + W] - te);
-        v[2] += fabs((double)b);
-        g -= gy * sgn1(b);
-      }
-      if (y > 0) g += gy * sgn1((pe - p[e - W]) - (te - t[e - W]));
-      dp[e] = g;
-    }
+    if (L1) dp[e] = ft_pixel(e, p, t, H, W, g0, gx, gy, v);
     if (!iq_valid(a, te)) continue;
     double q[3];
     iq_prob(a, pe, q);
@@ -436,18 +421,7 @@ __global__ __launch_bounds__(256) void k_iqsl_sums(const float* __restrict__ p,
     }
     v[13] += 1.0;
   }
-  __shared__ double red[4][kIqUsed];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kIqUsed; ++k) v[k] = wsum64(v[k]);
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < kIqUsed; ++k) red[wv][k] = v[k];
-  __syncthreads();
-  if (threadIdx.x < kIqUsed) {
-    const int k = threadIdx.x;
-    partials[blockIdx.x * kIqTerms + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-  }
+  block_sum_store(v, partials + blockIdx.x * kIqTerms);
 }
 
 // loss: [loss_l1, loss_grad, loss_iqsl, total] when L1, [loss_iqsl] otherwise
@@ -456,39 +430,24 @@ __global__ __launch_bounds__(256) void k_iqsl_finalize(double* __restrict__ part
                                                        double M, double Mx, double My, float lam,
                                                        float lam_iq, double ce_factor,
                                                        float* __restrict__ loss) {
-  __shared__ double sh[kIqUsed][256];
-  const int t = threadIdx.x;
-  double v[kIqUsed];
-#pragma unroll
-  for (int k = 0; k < kIqUsed; ++k) v[k] = 0.0;
-  for (int b = t; b < nblk; b += 256)
-#pragma unroll
-    for (int k = 0; k < kIqUsed; ++k) v[k] += partials[b * kIqTerms + k];
-#pragma unroll
-  for (int k = 0; k < kIqUsed; ++k) sh[k][t] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int k = 0; k < kIqUsed; ++k) sh[k][t] += sh[k][t + w];
-    __syncthreads();
-  }
-  if (t != 0) return;
+  double s[kIqUsed];
+  sum_partials(partials, nblk, kIqTerms, s);
+  if (threadIdx.x != 0) return;
   double* coef = partials + (long)nblk * kIqTerms;
   double dice = 0.0;
   for (int k = 0; k < 3; ++k) {
-    const double D = sh[6 + k][0] + sh[9 + k][0] + kIqEps, Nk = 2.0 * sh[3 + k][0] + kIqEps;
+    const double D = s[6 + k] + s[9 + k] + kIqEps, Nk = 2.0 * s[3 + k] + kIqEps;
     coef[k] = D;
     coef[3 + k] = Nk;
     dice += Nk / D;
   }
-  const double VV = 3.0 * sh[13][0] + kIqEps;
-  const double iq = (1.0 - dice / 3.0) + ce_factor * (-sh[12][0] / VV);
+  const double VV = 3.0 * s[13] + kIqEps;
+  const double iq = (1.0 - dice / 3.0) + ce_factor * (-s[12] / VV);
   coef[6] = VV;
   coef[7] = iq;
   if (L1) {
-    const float l1 = (float)(sh[0][0] / M);
-    const float lg = (float)(sh[1][0] / Mx) + (float)(sh[2][0] / My);
+    float l1, lg;
+    ft_losses(s, M, Mx, My, l1, lg);
     loss[0] = l1;
     loss[1] = lg;
     loss[2] = (float)iq;
@@ -526,7 +485,7 @@ __global__ __launch_bounds__(256) void k_iqsl_grad(const float* __restrict__ p,
     double r = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      s[k] = -(double)sgn1(pe - a.c[k]) / a.tau;
+      s[k] = -(double)sgn(pe - a.c[k]) / a.tau;
       r += q[k] * s[k];
     }
     double g = 0.0;
@@ -578,16 +537,14 @@ hipError_t launch_adapter_bwd(const float* prm, const float* noisy, const float*
 
 hipError_t launch_ft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
                           float lam, float* dpred, float* loss3, void* partials, hipStream_t s) {
-  const double M = (double)N * C * H * W;
-  const double Mx = (double)N * C * H * (W - 1), My = (double)N * C * (H - 1) * W;
-  // d/dp of mean|.| = sgn / numel; gradient_loss terms carry lambda_grad (finetune.py:285)
-  const float g0 = 1.0f / (float)M, gx = lam / (float)Mx, gy = lam / (float)My;
+  const FtScale f = ft_scale(N, C, H, W, lam);
   double* part = static_cast<double*>(partials);
-  hipLaunchKernelGGL(k_ft_loss, dim3(kFtBlocks), dim3(256), 0, s, pred, tgt, N, C, H, W, g0, gx, gy,
-                     dpred, part);
+  hipLaunchKernelGGL(k_ft_loss, dim3(kLossBlocks), dim3(256), 0, s, pred, tgt, N, C, H, W, f.g0,
+                     f.gx, f.gy, dpred, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_ft_finalize, dim3(1), dim3(256), 0, s, part, kFtBlocks, M, Mx, My, lam, loss3);
+  hipLaunchKernelGGL(k_ft_finalize, dim3(1), dim3(256), 0, s, part, kLossBlocks, f.M, f.Mx, f.My,
+                     lam, loss3);
   return hipGetLastError();
 }
 
@@ -597,31 +554,29 @@ hipError_t launch_iqsl_loss(const float* pred, const float* tgt, int N, int C, i
                             float lam, float lam_iq, const IqslScalars& a, double ce_factor,
                             bool with_l1, float* dpred, float* loss, void* partials,
                             hipStream_t s) {
-  const double M = (double)N * C * H * W;
-  const double Mx = (double)N * C * H * (W - 1), My = (double)N * C * (H - 1) * W;
-  const float g0 = 1.0f / (float)M, gx = lam / (float)Mx, gy = lam / (float)My;  // launch_ft_loss's
+  const FtScale f = ft_scale(N, C, H, W, lam);
   double* part = static_cast<double*>(partials);
-  const double* coef = part + (long)kFtBlocks * kIqTerms;
+  const double* coef = part + (long)kLossBlocks * kIqTerms;
   const long total = (long)N * C * H * W;
-  const dim3 grid(kFtBlocks), blk(256);
+  const dim3 grid(kLossBlocks), blk(256);
   hipError_t e;
   if (with_l1) {
-    hipLaunchKernelGGL(k_iqsl_sums<true>, grid, blk, 0, s, pred, tgt, N, C, H, W, g0, gx, gy, a,
-                       dpred, part);
+    hipLaunchKernelGGL(k_iqsl_sums<true>, grid, blk, 0, s, pred, tgt, N, C, H, W, f.g0, f.gx, f.gy,
+                       a, dpred, part);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_iqsl_finalize<true>, dim3(1), blk, 0, s, part, kFtBlocks, M, Mx, My, lam,
-                       lam_iq, ce_factor, loss);
+    hipLaunchKernelGGL(k_iqsl_finalize<true>, dim3(1), blk, 0, s, part, kLossBlocks, f.M, f.Mx,
+                       f.My, lam, lam_iq, ce_factor, loss);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (lam_iq == 0.f) return hipSuccess;
     hipLaunchKernelGGL(k_iqsl_grad<true>, grid, blk, 0, s, pred, tgt, total, a, lam_iq, ce_factor,
                        coef, dpred);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_iqsl_sums<false>, grid, blk, 0, s, pred, tgt, N, C, H, W, g0, gx, gy, a,
-                     dpred, part);
+  hipLaunchKernelGGL(k_iqsl_sums<false>, grid, blk, 0, s, pred, tgt, N, C, H, W, f.g0, f.gx, f.gy,
+                     a, dpred, part);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_iqsl_finalize<false>, dim3(1), blk, 0, s, part, kFtBlocks, M, Mx, My, lam,
-                     lam_iq, ce_factor, loss);
+  hipLaunchKernelGGL(k_iqsl_finalize<false>, dim3(1), blk, 0, s, part, kLossBlocks, f.M, f.Mx,
+                     f.My, lam, lam_iq, ce_factor, loss);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_iqsl_grad<false>, grid, blk, 0, s, pred, tgt, total, a, 1.f, ce_factor, coef,
                      dpred);

@@ -3,6 +3,7 @@
 #include <math.h>
 #include <cstdint>
 
+#include "block_reduce.h"
 #include "dn_internal.h"
 #include "philox.h"
 
@@ -318,32 +319,14 @@ __global__ __launch_bounds__(256) void k_poisson(const float* __restrict__ clean
 }
 
 // ------------------------------------------------------------------------------------
-// Loss reductions: fixed grid, per-block fp64 partial sums, one finalize block.
+// Loss reductions: fixed grid, per-block fp64 partial sums, one finalize block
+// (block_reduce.h).
 // ------------------------------------------------------------------------------------
-constexpr int kLossBlocks = 1024;
-constexpr int kLossTerms = 4;
-size_t loss_partials_bytes() { return sizeof(double) * kLossBlocks * kLossTerms; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int T>
-__device__ __forceinline__ void block_store_partials(double (&v)[T], double* partials) {
-  __shared__ double red[4][T];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < T; ++t) v[t] = wave_sum(v[t]);
-  if (lane == 0)
-#pragma unroll
-    for (int t = 0; t < T; ++t) red[wv][t] = v[t];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-      partials[blockIdx.x * kLossTerms + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-}
+size_t loss_partials_bytes() { return kLossPartialsBytes; }
+// every user asserts terms <= kLossStride (k_structure_loss's four are the most), so this covers
+// the last slot any of them writes
+static_assert(kLossPartialsBytes >= sizeof(double) * ((kLossBlocks - 1) * kLossStride + 4),
+              "dn_loss_partials_size() does not cover the widest loss");
 
 // training_script.md:141-153.  den1/den2 are the sub-images of the no-grad denoised output
 // (training_script.md:143-144), gathered here with the same rd_idx.
@@ -377,40 +360,15 @@ __global__ __launch_bounds__(256) void k_n2n_loss(const float* __restrict__ out,
     // autograd of mean(diff^2) + lambda*mean(q^2): (1/M)*(2*diff) + (lambda/M)*(2*q)
     dout[e] = __fadd_rn(__fmul_rn(invM, __fmul_rn(2.f, diff)), __fmul_rn(lamM, __fmul_rn(2.f, q)));
   }
-  block_store_partials<2>(v, partials);
-}
-
-// Sum of the first T terms of the block partials by one 256-thread block: thread t adds
-// blocks t, t+256, ... in order, then a fixed tree (deterministic; result valid in thread 0).
-template <int T>
-__device__ __forceinline__ void sum_partials(const double* __restrict__ partials, int nblk,
-                                             double (&out)[T]) {
-  __shared__ double sh[T][256];
-  const int t = threadIdx.x;
-  double v[T];
-#pragma unroll
-  for (int k = 0; k < T; ++k) v[k] = 0.0;
-  for (int b = t; b < nblk; b += 256)
-#pragma unroll
-    for (int k = 0; k < T; ++k) v[k] += partials[b * kLossTerms + k];
-#pragma unroll
-  for (int k = 0; k < T; ++k) sh[k][t] = v[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w)
-#pragma unroll
-      for (int k = 0; k < T; ++k) sh[k][t] += sh[k][t + w];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < T; ++k) out[k] = sh[k][0];
+  static_assert(2 <= kLossStride, "terms exceed the partials stride");
+  block_sum_store(v, partials + blockIdx.x * kLossStride);
 }
 
 __global__ __launch_bounds__(256) void k_n2n_finalize(const double* __restrict__ partials, int nblk,
                                                       double M, float lambda,
                                                       float* __restrict__ loss3) {
   double sums[2];
-  sum_partials<2>(partials, nblk, sums);
+  sum_partials(partials, nblk, kLossStride, sums);
   if (threadIdx.x != 0) return;
   const double s1 = sums[0], s2 = sums[1];
   const float l1 = (float)(s1 / M);
@@ -419,8 +377,6 @@ __global__ __launch_bounds__(256) void k_n2n_finalize(const double* __restrict__
   loss3[1] = l2;
   loss3[2] = l1 + l2;
 }
-
-__device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 // util.py:56-70 Structure_loss.  Per-element gradients are computed in gather form (each
 // element looks at its TV neighbours), so no atomics are needed.
@@ -438,23 +394,24 @@ __global__ __launch_bounds__(256) void k_structure_loss(
     const float d0 = p - tg, dc = p2 - tg;
     v[0] += fabs((double)d0);
     v[3] += fabs((double)dc);
-    float g2 = gc * sgnf(dc);
+    float g2 = gc * sgn(dc);
     if (y + 1 < H) {
       const float dv = pred2[e + W] - p2;  // tv1 term (y+1, y)
       v[1] += fabs((double)dv);
-      g2 -= gtv1 * sgnf(dv);
+      g2 -= gtv1 * sgn(dv);
     }
-    if (y > 0) g2 += gtv1 * sgnf(p2 - pred2[e - W]);
+    if (y > 0) g2 += gtv1 * sgn(p2 - pred2[e - W]);
     if (x + 1 < W) {
       const float dh = pred2[e + 1] - p2;  // tv2 term (x+1, x)
       v[2] += fabs((double)dh);
-      g2 -= gtv2 * sgnf(dh);
+      g2 -= gtv2 * sgn(dh);
     }
-    if (x > 0) g2 += gtv2 * sgnf(p2 - pred2[e - 1]);
-    dpred[e] = ga * sgnf(d0);
+    if (x > 0) g2 += gtv2 * sgn(p2 - pred2[e - 1]);
+    dpred[e] = ga * sgn(d0);
     dpred2[e] = g2;
   }
-  block_store_partials<4>(v, partials);
+  static_assert(4 <= kLossStride, "terms exceed the partials stride");
+  block_sum_store(v, partials + blockIdx.x * kLossStride);
 }
 
 __global__ __launch_bounds__(256) void k_structure_finalize(const double* __restrict__ partials,
@@ -462,7 +419,7 @@ __global__ __launch_bounds__(256) void k_structure_finalize(const double* __rest
                                                             double M2, float alpha, float beta,
                                                             float gamma, float* __restrict__ loss5) {
   double s[4];
-  sum_partials<4>(partials, nblk, s);
+  sum_partials(partials, nblk, kLossStride, s);
   if (threadIdx.x != 0) return;
   const float pix = (float)(s[0] / M), tv1 = (float)(s[1] / M1), tv2 = (float)(s[2] / M2),
               cst = (float)(s[3] / M);

@@ -18,6 +18,7 @@
 //   k_eval_finalize  fixed-order sum of the block partials -> metric (deterministic)
 #include <cstdint>
 
+#include "block_reduce.h"
 #include "dn_internal.h"
 
 namespace dn {
@@ -107,18 +108,7 @@ __global__ __launch_bounds__(256) void k_quantize_u8(const float* __restrict__ x
   }
 }
 
-// block-level sums (fixed shape: 256 threads, tree in LDS) -----------------------------
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) sh[t] += sh[t + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
+// block-level sums: block_tree_sum over the 256 threads (block_reduce.h) --------------------
 __global__ __launch_bounds__(256) void k_psnr_part(const uint8_t* __restrict__ a,
                                                    const uint8_t* __restrict__ b, long n,
                                                    double* __restrict__ part) {
@@ -128,14 +118,8 @@ __global__ __launch_bounds__(256) void k_psnr_part(const uint8_t* __restrict__ a
     const int d = (int)a[i] - (int)b[i];
     s += (unsigned long long)(d * d);
   }
-  const int t = threadIdx.x;
-  sh[t] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (t < k) sh[t] += sh[t + k];
-    __syncthreads();
-  }
-  if (t == 0) part[blockIdx.x] = (double)sh[0];  // exact below 2^53
+  const unsigned long long tot = block_tree_sum(s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = (double)tot;  // exact below 2^53
 }
 
 __global__ __launch_bounds__(256) void k_l1_part(const float* __restrict__ a,
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256) void k_l1_part(const float* __restrict__ a,
   double s = 0.0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     s += fabs((double)a[i] - (double)b[i]);
-  const double tot = block_sum_d(s, sh);
+  const double tot = block_tree_sum(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -159,7 +143,7 @@ __global__ __launch_bounds__(256) void k_l1_batched(const float* __restrict__ a,
   const float* pb = b + (long)blockIdx.x * n;
   double s = 0.0;
   for (long i = threadIdx.x; i < n; i += 256) s += fabs((double)pa[i] - (double)pb[i]);
-  const double tot = block_sum_d(s, sh);
+  const double tot = block_tree_sum(s, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = tot / (double)n;
 }
 
@@ -208,7 +192,7 @@ __global__ __launch_bounds__(256) void k_ssim_part(const uint8_t* __restrict__ a
     const double sg1 = s11 - mu1_sq, sg2 = s22 - mu2_sq, sg12 = s12 - mu12;
     s += ((2 * mu12 + C1) * (2 * sg12 + C2)) / ((mu1_sq + mu2_sq + C1) * (sg1 + sg2 + C2));
   }
-  const double tot = block_sum_d(s, sh);
+  const double tot = block_tree_sum(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -216,12 +200,10 @@ __global__ __launch_bounds__(256) void k_ssim_part(const uint8_t* __restrict__ a
 __global__ __launch_bounds__(256) void k_eval_finalize(const double* __restrict__ part, int nparts,
                                                        double count, int kind,
                                                        double* __restrict__ out) {
-  __shared__ double sh[256];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) v += part[i];  // fixed order per thread
-  const double s = block_sum_d(v, sh);
+  double s[1];
+  sum_partials(part, nparts, 1, s);
   if (threadIdx.x != 0) return;
-  const double mean = s / count;
+  const double mean = s[0] / count;
   out[0] = kind == 0 ? 10.0 * log10(255.0 * 255.0 / mean) : mean;
 }
 

@@ -7,7 +7,7 @@
 //                      partial, U = F / |F| (0 at |F| = 0) in place, inverse FFT along H, back to
 //                      the workspace -- the full spectrum never reaches HBM
 //   k_l1fft_rows_inv   half-spectrum -> real inverse along W, dpred = ga * sgn(D) + gb * result
-//   k_l1fft_finalize   fixed-order sum of the per-block fp64 partials -> loss3
+//   k_l1fft_finalize   the sum of the per-block fp64 partials -> loss3
 //
 // A transform length is L = m P with m odd, 1 <= m <= 31, and P = 2^k >= 8 (L <= 1024): one
 // Cooley-Tukey split in front of a radix-2 network.  With input index n = P n1 + n2 and output
@@ -28,6 +28,7 @@
 // is tw[n2 k1] (n2 k1 < L) and its m-point DFT matrix tw[(n1 k1 mod m) P].
 #include <hip/hip_runtime.h>
 
+#include "block_reduce.h"
 #include "dn_internal.h"
 
 namespace dn {
@@ -212,17 +213,9 @@ __device__ __forceinline__ void fft_run(float2* s, const float2* tw, const FftTi
   }
 }
 
-__device__ __forceinline__ float l1fft_sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-
-// the block's sum in a fixed order -> *out (one double per block); red: 4 doubles of LDS that no
-// thread reads or writes any more (the transform kernels lend their twiddle table, which keeps
-// the column pass at 40 KiB, four workgroups per CU)
-__device__ __forceinline__ void l1fft_block_sum(double v, double* red, double* out) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = ((red[0] + red[1]) + red[2]) + red[3];
-}
+// The block partials go through block_sum_store (block_reduce.h).  The transform kernels lend it
+// their twiddle table, dead by then, as its four doubles of LDS: that keeps the column pass at
+// 40 KiB, four workgroups per CU.
 
 // Row pair rp = rows 2rp, 2rp+1 of the flattened [N*C*H][W] image (H is even, so a pair never
 // straddles two planes).  z = rowA + i rowB; with Z = FFT(z): FA[k] = (Z[k] + conj Z[W-k]) / 2,
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_fwd(const float* __restrict_
     spec[(2 * rp) * Wh + k] = make_float2(0.5f * (z1.x + z2.x), 0.5f * (z1.y - z2.y));
     spec[(2 * rp + 1) * Wh + k] = make_float2(0.5f * (z1.y + z2.y), 0.5f * (z2.x - z1.x));
   }
-  l1fft_block_sum(acc, reinterpret_cast<double*>(tw), partials + blockIdx.x);
+  block_sum_store(acc, partials + blockIdx.x, reinterpret_cast<double*>(tw));
 }
 
 // Block = (plane, tile of TC adjacent half-spectrum columns); the last tile of a plane is ragged
@@ -304,7 +297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int k = k0 + c;
     if (k < Wh) base[(long)h * Wh + k] = s[fft_slot(h, t) * t.pitch + c];
   }
-  l1fft_block_sum(acc, reinterpret_cast<double*>(tw), partials + blockIdx.x);
+  block_sum_store(acc, partials + blockIdx.x, reinterpret_cast<double*>(tw));
 }
 
 // V (the column-inverse of U) is Hermitian along k in every row, so rows A and B of a pair come
@@ -343,8 +336,8 @@ __global__ __launch_bounds__(256) void k_l1fft_rows_inv(const float2* __restrict
     if (rp >= R) break;
     const float2 z = s[fft_slot(w, t) * t.pitch + p];
     const long e = 2 * rp * W + w;
-    dpred[e] = ga * l1fft_sgn(pred[e] - tgt[e]) + gb * z.x;
-    dpred[e + W] = ga * l1fft_sgn(pred[e + W] - tgt[e + W]) + gb * z.y;
+    dpred[e] = ga * sgn(pred[e] - tgt[e]) + gb * z.x;
+    dpred[e + W] = ga * sgn(pred[e + W] - tgt[e + W]) + gb * z.y;
   }
 }
 
@@ -358,40 +351,29 @@ __global__ __launch_bounds__(256) void k_l1fft_pixel(const float* __restrict__ p
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const float d = pred[e] - tgt[e];
     acc += fabs((double)d);
-    dpred[e] = ga * l1fft_sgn(d);
+    dpred[e] = ga * sgn(d);
   }
-  l1fft_block_sum(acc, red, partials + blockIdx.x);
+  block_sum_store(acc, partials + blockIdx.x, red);
 }
 
-// thread t adds blocks t, t + 256, ... in order, then a fixed tree: sums[0] over the first n0
-// partials (sum|D|), sums[1] over the next n1 (weighted sum|F|)
+// v[0] over the first n0 partials (sum|D|), v[1] over the next n1 (weighted sum|F|).  The two
+// segments differ in length, so the gather (thread t adds blocks t, t + 256, ... in order) is
+// written out here in place of sum_partials; the tree is the shared one.
 __global__ __launch_bounds__(256) void k_l1fft_finalize(const double* __restrict__ partials,
                                                         long n0, long n1, double denom,
                                                         float alpha, float beta,
                                                         float* __restrict__ loss3) {
   __shared__ double sh[2][256];
-  const int t = threadIdx.x;
-  double v0 = 0.0, v1 = 0.0;
-  for (long b = t; b < n0; b += 256) v0 += partials[b];
-  for (long b = t; b < n1; b += 256) v1 += partials[n0 + b];
-  sh[0][t] = v0;
-  sh[1][t] = v1;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      sh[0][t] += sh[0][t + w];
-      sh[1][t] += sh[1][t + w];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  const float pix = (float)(sh[0][0] / denom), frq = (float)(sh[1][0] / denom);
+  double v[2] = {0.0, 0.0};
+  for (long b = threadIdx.x; b < n0; b += 256) v[0] += partials[b];
+  for (long b = threadIdx.x; b < n1; b += 256) v[1] += partials[n0 + b];
+  block_tree_sum(v, sh);
+  if (threadIdx.x != 0) return;
+  const float pix = (float)(v[0] / denom), frq = (float)(v[1] / denom);
   loss3[0] = pix;
   loss3[1] = frq;
   loss3[2] = alpha * pix + beta * frq;
 }
-
-constexpr int kL1Blocks = 1024;  // the beta == 0 path's fixed grid
 
 // L = m 2^k with m odd, m <= 31, k >= 3, L <= 1024
 bool l1fft_len_ok(int v) {
@@ -419,7 +401,7 @@ bool l1fft_plan(int N, int C, int H, int W, L1fftPlan& p) {
   p.nblk_cols = planes * p.ntile;
   if (p.nblk_rows >= (1L << 31) || p.nblk_cols >= (1L << 31)) return false;
   p.spec_bytes = (size_t)planes * H * Wh * sizeof(float2);
-  const long nparts = p.nblk_rows + p.nblk_cols > kL1Blocks ? p.nblk_rows + p.nblk_cols : kL1Blocks;
+  const long nparts = p.nblk_rows + p.nblk_cols > kLossBlocks ? p.nblk_rows + p.nblk_cols : kLossBlocks;
   p.total_bytes = p.spec_bytes + (size_t)nparts * sizeof(double);
   return true;
 }
@@ -446,10 +428,10 @@ hipError_t launch_l1fft_loss(const float* pred, const float* tgt, int N, int C, 
   double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + p.spec_bytes);
   hipError_t e;
   if (beta == 0.f) {
-    hipLaunchKernelGGL(k_l1fft_pixel, dim3(kL1Blocks), dim3(256), 0, s, pred, tgt,
+    hipLaunchKernelGGL(k_l1fft_pixel, dim3(kLossBlocks), dim3(256), 0, s, pred, tgt,
                        (long)N * C * H * W, ga, dpred, part);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_l1fft_finalize, dim3(1), dim3(256), 0, s, part, (long)kL1Blocks, 0L,
+    hipLaunchKernelGGL(k_l1fft_finalize, dim3(1), dim3(256), 0, s, part, (long)kLossBlocks, 0L,
                        denom, alpha, beta, loss3);
     return hipGetLastError();
   }

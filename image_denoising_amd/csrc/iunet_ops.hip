@@ -15,6 +15,7 @@
 //   small elementwise ops: view add, LeakyReLU' mask, sigmoid' of the output
 #include <math.h>
 
+#include "block_reduce.h"
 #include "dn_internal.h"
 #include "iunet_ops.h"
 
@@ -165,10 +166,8 @@ __global__ __launch_bounds__(64) void k_gn_dparams(const double* __restrict__ pa
     dg += (s2 - mean * s1) * rstd;
     dbt += s1;
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    dg += __shfl_xor(dg, o, 64);
-    dbt += __shfl_xor(dbt, o, 64);
-  }
+  dg = wave_sum(dg);
+  dbt = wave_sum(dbt);
   if (l == 0) {
     dgamma[c] = (float)dg;
     dbeta[c] = (float)dbt;

@@ -14,6 +14,7 @@
 //    thin 3x3 convolutions on the vector ALUs, and the parameter gradients (slab rows per
 //    workgroup, summed in a fixed order in fp64).  No atomics anywhere.
 // 3. The Hann-window blend of patchwise inference in gather form.
+#include "block_reduce.h"
 #include "dn_internal.h"
 
 namespace dn {
@@ -168,20 +169,6 @@ constexpr int MA_WMAX = 1024;    // widest row whose DFT twiddle table lives in 
 constexpr int MA_NBMAX = 8;      // most frequency bands
 constexpr int MA_WG_BLOCKS = 256;  // most workgroups (slab rows) of a weight-gradient launch
 
-__device__ __forceinline__ double ma_wsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the 256 threads in a fixed order, returned to all of them
-__device__ __forceinline__ double ma_bsum(double v, double* red) {
-  v = ma_wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // (cos, sin)(2 pi k / W), k < W, for rows too wide for the LDS table
 __global__ __launch_bounds__(256) void k_ma_twiddle(int W, double* __restrict__ tw) {
   const int k = blockIdx.x * 256 + threadIdx.x;
@@ -209,13 +196,13 @@ __global__ __launch_bounds__(256) void k_ma_stats(const float* __restrict__ nois
   const int NF = 6 + 3 * nb;
   double s = 0.0;
   for (long e = tid; e < M; e += 256) s += (double)x[e];
-  const double mean = ma_bsum(s, red) / (double)M;
+  const double mean = block_sum(s, red) / (double)M;
   s = 0.0;
   for (long e = tid; e < M; e += 256) {
     const double d = (double)x[e] - mean;
     s += d * d;
   }
-  const double var = ma_bsum(s, red) / (double)(M - 1);  // unbiased, torch.std's default
+  const double var = block_sum(s, red) / (double)(M - 1);  // unbiased, torch.std's default
   if (tid == 0) {
     feat[(long)b * NF + 2 * t] = (float)mean;
     feat[(long)b * NF + 2 * t + 1] = (float)sqrt(var);
@@ -478,8 +465,8 @@ __global__ __launch_bounds__(256) void k_ma_conv(MaConvArgs a) {
       }
     }
     if (MODE == MA_DFINAL) {
-      const double s0 = ma_bsum((double)rd, red);
-      const double s1 = ma_bsum((double)dp, red);
+      const double s0 = block_sum((double)rd, red);
+      const double s1 = block_sum((double)dp, red);
       if (threadIdx.x == 0) {
         double* p = a.part + (((long)n * CO + o) * gridDim.x + blockIdx.x) * 2;
         p[0] = s0;
