@@ -804,7 +804,7 @@ dn_status dn_conv2d_backward_data(const float* dz, int N, int H, int W, int Cout
 
 size_t dn_conv2d_wgrad_slab_size(int N, int H, int W, int Cin, int Cout, int ksize) {
   const int mode = ksize == 3 ? W_C3 : W_C1;
-  return sizeof(float) * (64 + (size_t)wgrad_slab_floats(mode, N, H, W, Cin, Cout));
+  return sizeof(float) * (64 + (size_t)wgrad_size(mode, N, H, W, Cin, Cout, false).floats);
 }
 
 dn_status dn_conv2d_backward_weight(const float* dz, const float* x, int x_stride, int N, int H,
@@ -813,27 +813,20 @@ dn_status dn_conv2d_backward_weight(const float* dz, const float* x, int x_strid
   if (!dz || !x || !dwb || !slab) return fail(DN_ERR_ARG, "null argument");
   if (ksize != 1 && ksize != 3) return fail(DN_ERR_ARG, "ksize must be 1 or 3");
   const int mode = ksize == 3 ? W_C3 : W_C1;
-  if (!wgrad_supported(mode, Cout, Cin)) return fail(DN_ERR_ARG, "unsupported Cout");
+  if (!wgrad_supported(mode, Cout)) return fail(DN_ERR_ARG, "unsupported Cout");
   if (mode == W_C1 && Cin > 96) return fail(DN_ERR_ARG, "1x1 wgrad supports Cin <= 96");
-  const int sp = wgrad_splits(mode, N, H, W, Cin, Cout);
-  return hip_status(wgrad(mode, View{const_cast<float*>(dz), Cout, 0},
-                          View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cout, Cin, dwb,
-                          static_cast<float*>(slab), sp, (hipStream_t)stream),
-                    "dn_conv2d_backward_weight");
+  return wgrad_run(wgrad_route(wgrad_shape(mode, N, H, W, Cin, Cout, Cout, 0, x_stride, 0)), dz, x,
+                   dwb, static_cast<float*>(slab), nullptr, (hipStream_t)stream);
 }
 
 dn_status dn_conv2d_backward_weight_x6(const float* dz, const float* x, int x_stride, int N,
                                        int H, int W, int Cin, int Cout, float* dwb, void* slab,
                                        void* stream) {
   if (!dz || !x || !dwb || !slab) return fail(DN_ERR_ARG, "null argument");
-  if (!wgrad_supported(W_C3, Cout, Cin)) return fail(DN_ERR_ARG, "unsupported Cout");
-  const int sp = wgrad_splits(W_C3, N, H, W, Cin, Cout);
-  // (dn_profile_ops: wgrad() takes the "wgrad3" record itself; k_reduce_batch sets no label, so
-  // the record keeps the GEMM kernel's)
-  return hip_status(wgrad(W_C3, View{const_cast<float*>(dz), Cout, 0},
-                          View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cout, Cin, dwb,
-                          static_cast<float*>(slab), sp, (hipStream_t)stream, true),
-                    "dn_conv2d_backward_weight_x6");
+  if (!wgrad_supported(W_C3, Cout)) return fail(DN_ERR_ARG, "unsupported Cout");
+  // (dn_profile_ops: wgrad_run() takes the "wgrad3" record itself)
+  return wgrad_run(wgrad_route(wgrad_shape(W_C3, N, H, W, Cin, Cout, Cout, 0, x_stride, 0, true)),
+                   dz, x, dwb, static_cast<float*>(slab), nullptr, (hipStream_t)stream);
 }
 
 dn_status dn_deconv2x2_forward(const float* x, int N, int H, int W, int Cin, const float* w,
@@ -907,19 +900,16 @@ dn_status dn_deconv2x2_backward_data(const float* dy, int dy_stride, int N, int 
 }
 
 size_t dn_deconv2x2_wgrad_slab_size(int N, int H, int W, int Cin, int Cout) {
-  return sizeof(float) * (64 + (size_t)wgrad_slab_floats(W_UP2, N, H, W, Cin, Cout));
+  return sizeof(float) * (64 + (size_t)wgrad_size(W_UP2, N, H, W, Cin, Cout, false).floats);
 }
 
 dn_status dn_deconv2x2_backward_weight(const float* dy, int dy_stride, const float* x, int N, int H,
                                        int W, int Cin, int Cout, float* dwb, void* slab,
                                        void* stream) {
   if (!dy || !x || !dwb || !slab) return fail(DN_ERR_ARG, "null argument");
-  if (!wgrad_supported(W_UP2, Cout, Cin)) return fail(DN_ERR_ARG, "unsupported Cout");
-  const int sp = wgrad_splits(W_UP2, N, H, W, Cin, Cout);
-  return hip_status(wgrad(W_UP2, View{const_cast<float*>(dy), dy_stride, 0},
-                          View{const_cast<float*>(x), Cin, 0}, N, H, W, Cout, Cin, dwb,
-                          static_cast<float*>(slab), sp, (hipStream_t)stream),
-                    "dn_deconv2x2_backward_weight");
+  if (!wgrad_supported(W_UP2, Cout)) return fail(DN_ERR_ARG, "unsupported Cout");
+  return wgrad_run(wgrad_route(wgrad_shape(W_UP2, N, H, W, Cin, Cout, dy_stride, 0, Cin, 0)), dy, x,
+                   dwb, static_cast<float*>(slab), nullptr, (hipStream_t)stream);
 }
 
 dn_status dn_maxpool2x2_forward(const float* x, int N, int H, int W, int C, float* y, int y_stride,
@@ -1257,7 +1247,7 @@ dn_status dn_groupnorm_backward(const float* dy, int dy_stride, int dy_off, cons
 size_t dn_conv2d_wgrad_blocked_slab_size(int N, int H, int W, int Cin, int Cout, int ksize) {
   if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (ksize != 1 && ksize != 3)) return 0;
   const int mode = ksize == 3 ? W_C3 : W_C1;
-  return sizeof(float) * (64 + (size_t)gwgrad_slab_floats(mode, N, H, W, Cin, Cout));
+  return sizeof(float) * (64 + (size_t)wgrad_size(mode, N, H, W, Cin, Cout, true).floats);
 }
 
 dn_status dn_conv2d_backward_weight_blocked(const float* g, int g_stride, int g_off,
@@ -1277,12 +1267,11 @@ dn_status dn_conv2d_backward_weight_blocked(const float* g, int g_stride, int g_
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const StreamDeviceGuard device_guard(s);
   const int mode = ksize == 3 ? W_C3 : W_C1;
-  // (k_reduce_batch sets no label: the record keeps the GEMM kernel's)
-  const OpTimer timer(s, ksize == 3 ? "wgrad3" : "wgrad1",
-                      2.0 * N * H * W * (double)Cout * Cin * ksize * ksize, Cin, Cout, H, W, N);
-  return gwgrad_run(mode, View{const_cast<float*>(g), g_stride, g_off},
-                    View{const_cast<float*>(x), x_stride, x_off}, N, H, W, Cin, Cout, bias != 0,
-                    precision, dwb, static_cast<float*>(slab), s);
+  WgradShape sh = wgrad_shape(mode, N, H, W, Cin, Cout, g_stride, g_off, x_stride, x_off,
+                              precision == DN_PREC_FP32_X6);
+  sh.blocked = true;
+  sh.bias = bias != 0;
+  return wgrad_run(wgrad_route(sh), g, x, dwb, static_cast<float*>(slab), nullptr, s);
   DN_GUARD_END
 }
 

@@ -1256,251 +1256,74 @@ hipError_t launch_fwd_nt(int gather, int nt, const FwdArgs& a, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
+// ---- weight-gradient launchers: the route (wgrad_route.cpp) has decided everything ----
 template <int MODE, int MF, int NW, int CIF>
-static hipError_t run_wgrad(const WgradArgs& a, int splits, hipStream_t s) {
+static hipError_t run_wgrad(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
   using C = WgCfg<MODE, MF, NW, CIF>;
-  const int nz = a.zc > 0 ? (a.cout_total + a.zc - 1) / a.zc : 1;
-  dim3 grid(splits, (a.Cin + C::CIN_T - 1) / C::CIN_T, nz);
+  if (C::CIN_T != r.cib) return hipErrorInvalidValue;
+  dim3 grid(r.splits, (a.Cin + C::CIN_T - 1) / C::CIN_T, r.nz);
   hipLaunchKernelGGL((k_wgrad<MODE, MF, NW, CIF>), grid, dim3(C::NTHR), 0, s, a);
   return hipGetLastError();
 }
 
-template <int CO_FR, int WM, int WN>
-static hipError_t run_wgrad3(const WgradArgs& a, int splits, hipStream_t s) {
-  using C = Wg3Cfg<CO_FR, WM, WN>;
-  const int nz = a.zc > 0 ? (a.cout_total + a.zc - 1) / a.zc : 1;
-  dim3 grid(splits, (a.Cin + C::CIB - 1) / C::CIB, nz);
-  // K stage width: 32-pixel row segments, or 16 / 8 / 4 pixels x 2 / 4 / 8 rows for narrow images
-  prof_kernel("k_wgrad3");
-  if (a.KW >= 32) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 5>), grid, dim3(C::NTHR), 0, s, a);
-  else if (a.KW >= 16) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 4>), grid, dim3(C::NTHR), 0, s, a);
-  else if (a.KW >= 8) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 3>), grid, dim3(C::NTHR), 0, s, a);
-  else hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 2>), grid, dim3(C::NTHR), 0, s, a);
-  return hipGetLastError();
-}
-
-// the asynchronous 3x3 kernel needs 16-byte aligned pixels and channel quads that stay
-// inside each pixel's row (reads past Cin land on padding or a neighbouring slice)
-static bool wgrad3_ok(const WgradArgs& a) {
-  if (a.Cout != 48 && a.Cout != 96) return false;
-  if (a.Cin < 32) return false;  // a 32/48-channel block would be mostly padding
-  if ((a.g_stride | a.g_off | a.x_stride | a.x_off) & 3) return false;
-  if (a.x_off + ((a.Cin + 3) & ~3) > a.x_stride) return false;
-  return a.zeros != nullptr;
-}
-
-// (CIN_T, PR, PC) of the template that launch_wgrad picks for (mode, cout)
-static void wgrad_tile(int mode, int cout, int& cin_t, int& pr, int& pc) {
-  const int cf = (cout + 15) / 16;
-  pc = 32;
-  if (mode == W_C3) { cin_t = cf >= 6 ? 32 : 48; pr = 1; }
-  else if (mode == W_UP2) { cin_t = 16; pr = 1; pc = 16; }
-  else { cin_t = cf == 1 ? 32 : 96; pr = cf >= 6 ? 1 : 2; }
-}
-
-bool wgrad_supported(int mode, int cout, int cin) {
-  (void)cin;
-  const int cf = (cout + 15) / 16;
-  if (mode == W_C3 || mode == W_UP2) return cf == 3 || cf == 6;
-  if (mode == W_C1) return cf == 1 || cf == 6;
-  return false;
-}
-
-// Splits: splits x input-channel blocks fills ONE round of resident workgroups (3 per CU on
-// 256 CUs) without a straggler round (floor, not ceil: 770 workgroups on 768 slots would
-// double the time), at least two pixel chunks each, and a slab of at most 256 MB.
-int wgrad_splits(int mode, int N, int KH, int KW, int Cin, int Cout) {
-  int cin_t, pr, pc;
-  wgrad_tile(mode, Cout, cin_t, pr, pc);
-  const int taps = mode == W_C3 ? 9 : (mode == W_UP2 ? 4 : 1);
-  long units = (long)N * ((KH + pr - 1) / pr) * ((KW + pc - 1) / pc);
-  if (mode == W_C3 && KW < 32) {  // k_wgrad3 stages rows of narrow images together
-    const int sw = KW >= 16 ? 16 : (KW >= 8 ? 8 : 4), sh = 32 / sw;
-    units = (long)N * ((KH + sh - 1) / sh) * ((KW + sw - 1) / sw);
-  }
-  const long cib = (Cin + cin_t - 1) / cin_t;
-  long want = 768 / cib;
-  const long slab_cap = (64L << 20) / ((long)Cout * Cin * taps + Cout);  // <= 256 MB of slab
-  if (want > slab_cap) want = slab_cap;
-  // at least 2 pixel chunks per split: on the small levels the per-workgroup slab (up to 110 KB
-  // written, then re-read by the reduction) outweighs the work of a 1-chunk split
-  if (want > units / 2) want = units / 2;
-  if (want < 1) want = 1;
-  return (int)want;
-}
-
-hipError_t launch_wgrad(int mode, const WgradArgs& a, int splits, hipStream_t s, bool x6) {
-  const int cf = (a.Cout + 15) / 16;
-  if (x6 && mode == W_C3 && wgrad3_x6_ok(a)) return launch_wgrad3_x6(a, splits, s);
-  if (mode == W_C3 && wgrad3_ok(a)) {
-    if (cf == 6) return run_wgrad3<6, 2, 2>(a, splits, s);
-    if (cf == 3) return run_wgrad3<3, 1, 3>(a, splits, s);
-  }
+hipError_t launch_wgrad(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
+  const int mode = r.sh.mode, cf = r.co_fr;
+  if (r.kernel != WK_WGRAD) return hipErrorInvalidValue;
   if (mode == W_C3) {
-    if (cf == 3) return run_wgrad<W_C3, 1, 3, 1>(a, splits, s);
-    if (cf == 6) return run_wgrad<W_C3, 2, 3, 1>(a, splits, s);
+    if (cf == 3) return run_wgrad<W_C3, 1, 3, 1>(a, r, s);
+    if (cf == 6) return run_wgrad<W_C3, 2, 3, 1>(a, r, s);
   } else if (mode == W_C1) {
-    if (cf == 1) return run_wgrad<W_C1, 1, 1, 2>(a, splits, s);
-    if (cf == 6) return run_wgrad<W_C1, 2, 3, 6>(a, splits, s);
+    if (cf == 1) return run_wgrad<W_C1, 1, 1, 2>(a, r, s);
+    if (cf == 6) return run_wgrad<W_C1, 2, 3, 6>(a, r, s);
   } else if (mode == W_UP2) {
-    if (cf == 3) return run_wgrad<W_UP2, 1, 3, 1>(a, splits, s);
-    if (cf == 6) return run_wgrad<W_UP2, 2, 3, 1>(a, splits, s);
+    if (cf == 3) return run_wgrad<W_UP2, 1, 3, 1>(a, r, s);
+    if (cf == 6) return run_wgrad<W_UP2, 2, 3, 1>(a, r, s);
   }
   return hipErrorInvalidValue;
 }
 
-// ---- general weight gradient (any Cout via output-channel blocks) ----------------------
-// 3x3: k_wgrad3 in blocks of 96 / 48 / 32 output channels (Cin >= 16, float4-aligned views);
-// 1x1: k_wgrad<W_C1> in blocks of 96 / 48.  Every block of one layer uses the same split count,
-// so each slab row ends up holding the whole [W ; b] image and one reduction job finishes it.
-static int gw_block(int mode, int cout) {
-  if (mode == W_C3) return cout <= 32 ? 32 : (cout <= 48 ? 48 : 96);
-  return cout <= 48 ? 48 : 96;
-}
-
-// input channels per workgroup of the 3x3 kernel: 32 for 96-wide output blocks; for 32-wide
-// blocks (RDB growth convs, 24-channel layers) 32 / 48 / 64, whichever pads Cin least (ties:
-// the wider block, fewer workgroups re-reading the gradient operand); else 48
-static int gw_cin_t(int cb, int Cin) {
-  if (cb == 96) return 32;
-  if (cb == 48) return 48;
-  int best = 48;
-  long pad = 1L << 30;
-  for (int t : {64, 48, 32}) {
-    const long p = (long)(Cin + t - 1) / t * t;
-    if (p < pad) { pad = p; best = t; }
-  }
-  return best;
-}
-
-int gwgrad_splits(int mode, int N, int KH, int KW, int Cin, int Cout) {
-  const int cb = gw_block(mode, Cout);
-  const int nblk = (Cout + cb - 1) / cb;
-  const int cin_t = mode == W_C3 ? gw_cin_t(cb, Cin) : 96;
-  if (mode == W_C1) {  // k_wgrad1: one 32-pixel row segment per K stage
-    const long units = (long)N * KH * ((KW + 31) / 32);
-    long want = 768 / ((long)nblk * ((Cin + 95) / 96));
-    const long slab_cap = (64L << 20) / ((long)Cout * Cin + Cout);
-    if (want > slab_cap) want = slab_cap;
-    if (want > units / 2) want = units / 2;
-    return (int)(want < 1 ? 1 : want);
-  }
-  const long cib = (long)nblk * ((Cin + cin_t - 1) / cin_t);
-  const int taps = mode == W_C3 ? 9 : 1;
-  const int sw = KW >= 32 ? 32 : (KW >= 16 ? 16 : (KW >= 8 ? 8 : 4));  // k_wgrad3 segments
-  const long units = mode == W_C3 ? (long)N * ((KH + 32 / sw - 1) / (32 / sw)) * ((KW + sw - 1) / sw)
-                                  : (long)N * ((KH + (cb == 96 ? 0 : 1)) / (cb == 96 ? 1 : 2)) * ((KW + 31) / 32);
-  long want = 768 / cib;
-  const long slab_cap = (64L << 20) / ((long)Cout * Cin * taps + Cout);
-  if (want > slab_cap) want = slab_cap;
-  if (want > units / 2) want = units / 2;
-  return (int)(want < 1 ? 1 : want);
-}
-
-// operands are read as channel quads: every quad that starts inside [0, C) must lie inside
-// the view's row (padding channels of a wider buffer are fine, they meet masked rows/columns)
-bool gwgrad_ok(int mode, int Cin, int Cout, const View& g, const View& x) {
-  if (mode != W_C3 && mode != W_C1) return false;
-  if ((g.stride | g.off | x.stride | x.off) & 3) return false;
-  if (mode == W_C3 && Cin < 16) return false;
-  if (x.off + ((Cin + 3) & ~3) > x.stride || g.off + ((Cout + 3) & ~3) > g.stride) return false;
-  return Cout >= 1 && Cin >= 1;
-}
-
-hipError_t launch_gwgrad(int mode, const WgradArgs& a0, int splits, hipStream_t s) {
-  const int cb = gw_block(mode, a0.Cout);
-  WgradArgs a = a0;  // all output-channel blocks in ONE launch (blockIdx.z)
-  a.zc = cb;
-  a.cout_total = a0.Cout;
-  a.co_base = 0;
-  if (mode == W_C3) {
-    if (cb == 96) return run_wgrad3<6, 2, 2>(a, splits, s);
-    if (cb == 48) return run_wgrad3<3, 1, 3>(a, splits, s);
-    const int ct = gw_cin_t(cb, a.Cin);
-    if (ct == 64) return run_wgrad3<2, 1, 4>(a, splits, s);
-    if (ct == 32) return run_wgrad3<2, 1, 2>(a, splits, s);
-    return run_wgrad3<2, 1, 3>(a, splits, s);
-  }
-  // 1x1: the asynchronous k_wgrad1 tiled over (input-channel block of 96, output-channel block)
-  const dim3 grid(splits, (a.Cin + 95) / 96, (a.Cout + cb - 1) / cb);
-  prof_kernel(cb == 96 ? "k_wgrad1<6,6,2,2>" : "k_wgrad1<3,6,1,3>");
-  if (cb == 96) hipLaunchKernelGGL((k_wgrad1<6, 6, 2, 2>), grid, dim3(256), 0, s, a, 0);
-  else hipLaunchKernelGGL((k_wgrad1<3, 6, 1, 3>), grid, dim3(192), 0, s, a, 0);
+template <int CO_FR, int WM, int WN>
+static hipError_t run_wgrad3(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
+  using C = Wg3Cfg<CO_FR, WM, WN>;
+  dim3 grid(r.splits, (a.Cin + C::CIB - 1) / C::CIB, r.nz);
+  prof_kernel("k_wgrad3");
+  if (r.swl == 5) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 5>), grid, dim3(C::NTHR), 0, s, a);
+  else if (r.swl == 4) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 4>), grid, dim3(C::NTHR), 0, s, a);
+  else if (r.swl == 3) hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 3>), grid, dim3(C::NTHR), 0, s, a);
+  else hipLaunchKernelGGL((k_wgrad3<CO_FR, WM, WN, 2>), grid, dim3(C::NTHR), 0, s, a);
   return hipGetLastError();
 }
 
-// ---- k_wgrad1 routing --------------------------------------------------------------
-static bool wgrad1_shape(int mode, int cin, int cout) {
-  return (mode == W_C1 || mode == W_UP2) && cin == cout && (cin == 96 || cin == 48);
+// 96 / 48 / 32 outputs per workgroup x 32 / 48 / (32, 48 or 64) input channels
+hipError_t launch_wgrad3(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
+  if (r.kernel != WK_WGRAD3) return hipErrorInvalidValue;
+  if (r.co_fr == 6 && r.cib == 32) return run_wgrad3<6, 2, 2>(a, r, s);
+  if (r.co_fr == 3 && r.cib == 48) return run_wgrad3<3, 1, 3>(a, r, s);
+  if (r.co_fr == 2 && r.cib == 64) return run_wgrad3<2, 1, 4>(a, r, s);
+  if (r.co_fr == 2 && r.cib == 32) return run_wgrad3<2, 1, 2>(a, r, s);
+  if (r.co_fr == 2 && r.cib == 48) return run_wgrad3<2, 1, 3>(a, r, s);
+  return hipErrorInvalidValue;
 }
 
-bool wgrad1_ok(int mode, const WgradArgs& a) {
-  if (!wgrad1_shape(mode, a.Cin, a.Cout) || !a.zeros) return false;
-  if ((a.g_stride | a.g_off | a.x_stride | a.x_off) & 3) return false;
-  return a.g_off + a.Cout <= a.g_stride && a.x_off + a.Cin <= a.x_stride;
-}
-
-// one round of resident workgroups (3 per CU) over splits x parities, >= 2 segments each
-int wgrad1_splits(int mode, int N, int KH, int KW) {
-  const int z = mode == W_UP2 ? 4 : 1;
-  const long units = (long)N * KH * ((KW + 31) / 32);
-  long sp = 768 / z;
-  if (sp > units / 2) sp = units / 2;
-  // UP2: whole groups of 8 (k_wgrad1p's XCD map of the four parity blocks; splits past the
-  // pixel count write zero rows)
-  if (z == 4) sp = sp < 8 ? 8 : sp / 8 * 8;
-  return (int)(sp < 1 ? 1 : sp);
-}
-
-long wgrad_slab_floats(int mode, int N, int KH, int KW, int cin, int cout) {
-  const int taps = mode == W_C3 ? 9 : (mode == W_UP2 ? 4 : 1);
-  long f = (long)wgrad_splits(mode, N, KH, KW, cin, cout) * ((long)cout * cin * taps + cout);
-  if (wgrad1_shape(mode, cin, cout)) {
-    const long f1 = (long)(mode == W_UP2 ? 4 : 1) * wgrad1_splits(mode, N, KH, KW) *
-                    ((long)cout * cin + cout);
-    if (f1 > f) f = f1;
-  }
-  return f;
-}
-
-// k_wgrad1 + its reductions straight into dwb (PyTorch layout, bias after the weight); x6: the
-// 96 x 96 1x1 on k_wgrad1p (bf16x6), the same splits and slab rows
-hipError_t launch_wgrad1(int mode, const WgradArgs& a0, float* dwb, hipStream_t s,
-                         RedBatch* rb, bool x6) {
-  const bool up2 = mode == W_UP2;
-  const int sp = wgrad1_splits(mode, a0.N, a0.KH, a0.KW), z = up2 ? 4 : 1;
-  const long W = (long)a0.Cout * a0.Cin, row = W + a0.Cout;
-  WgradArgs a = a0;
-  a.slab_stride = row;
-  a.wlayout = up2 ? 1 : 0;  // deconv weight (in, out, 2, 2): [ci][co] per parity
-  const dim3 grid(sp, 1, z);
-  hipError_t e;
-  const bool p1 = x6 && wgrad1p_ok(a);
-  // head_gnb (g = nb, the gradient recomputed; nin_c's rows in hd_slab_c): k_wgrad1p only
-  if (a.head_gnb > 0 && !p1) return hipErrorInvalidValue;
-  if (p1) {
-    e = launch_wgrad1p(a, sp, s, up2);
+// The asynchronous k_wgrad1.  Fixed family: one 96 x 96 or 48 x 48 block, blockIdx.z = the deconv's
+// parity.  Blocked family: tiled over (input-channel block of 96, output-channel block), and
+// only these launches carry a profiler label.
+hipError_t launch_wgrad1(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
+  if (r.kernel != WK_WGRAD1) return hipErrorInvalidValue;
+  const int up2 = r.sh.mode == W_UP2;
+  const dim3 grid(r.splits, (a.Cin + r.cib - 1) / r.cib, r.zc ? r.nz : r.par);
+  if (r.co_fr == 6 && r.cib == 96) {
+    if (r.zc) prof_kernel("k_wgrad1<6,6,2,2>");
+    hipLaunchKernelGGL((k_wgrad1<6, 6, 2, 2>), grid, dim3(256), 0, s, a, up2);
+  } else if (r.co_fr == 3 && r.cib == 96) {
+    prof_kernel("k_wgrad1<3,6,1,3>");
+    hipLaunchKernelGGL((k_wgrad1<3, 6, 1, 3>), grid, dim3(192), 0, s, a, up2);
+  } else if (r.co_fr == 3 && r.cib == 48) {
+    hipLaunchKernelGGL((k_wgrad1<3, 3, 1, 3>), grid, dim3(192), 0, s, a, up2);
   } else {
-    if (a.Cout == 96)
-      hipLaunchKernelGGL((k_wgrad1<6, 6, 2, 2>), grid, dim3(256), 0, s, a, (int)up2);
-    else
-      hipLaunchKernelGGL((k_wgrad1<3, 3, 1, 3>), grid, dim3(192), 0, s, a, (int)up2);
-    e = hipGetLastError();
+    return hipErrorInvalidValue;
   }
-  if (e != hipSuccess) return e;
-  if (!up2 && a.hd_slab_c) {  // nin_c's weight gradient formed by the same launch (k_wgrad1p GNB)
-    const long rc = (long)a.head_gnb * 96 + a.head_gnb;
-    e = launch_reduce(a.hd_slab_c, rc, sp, rc, a.hd_dwc, s, rb);
-    if (e != hipSuccess) return e;
-  }
-  if (!up2) return launch_reduce(a.slab, row, sp, row, dwb, s, rb);
-  // W[ci][co][a][b] in output order: element e = 4 (ci*Cout + co) + ab lives in parity ab's
-  // block of sp rows
-  RedJob j = red_job(a.slab, row, sp, 4 * W, dwb);
-  j.ig = 4; j.is1 = 1; j.is2 = (int)(sp * row);
-  e = red_add(rb, j, s);
-  if (e != hipSuccess) return e;
-  return launch_reduce(a.slab + W, row, 4 * sp, a.Cout, dwb + 4 * W, s, rb);  // bias: all rows
+  return hipGetLastError();
 }
 
 RedJob red_job(const float* slab, long stride, int splits, long n, float* out) {

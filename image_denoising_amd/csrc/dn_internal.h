@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "wgrad_route.h"
+
 namespace dn {
 
 // Makes the device of stream s current for the lifetime of the guard (and restores the caller's
@@ -365,37 +367,22 @@ hipError_t launch_deconv_x6(const FwdArgs& a, const void* wimg, hipStream_t s, b
 // (pack_job_deconv_dgrad_x6, 4 x X6_HEAD_BF bf16)
 bool deconv_dgrad_x6_ok(const FwdArgs& a);
 hipError_t launch_deconv_dgrad_x6(const FwdArgs& a, const void* wimg, hipStream_t s);
-int wgrad_splits(int mode, int N, int KH, int KW, int Cin, int Cout);
-hipError_t launch_wgrad(int mode, const WgradArgs& a, int splits, hipStream_t s, bool x6 = false);
-// bf16x6 3x3 weight gradient (conv_x6.hip, k_wgrad3s): 96 or 48 outputs, Cin >= 32
-bool wgrad3_x6_ok(const WgradArgs& a);
-int wgrad_splits_x6(const WgradArgs& a, int splits);  // split count when the x6 kernel is taken
-hipError_t launch_wgrad3_x6(const WgradArgs& a, int splits, hipStream_t s);
-// ... its 96-output form with the operands split once per stage into LDS planes (wgrad_x6p.hip,
-// k_wgrad3p; nz = output-channel blocks of a.zc == 96 over blockIdx.z, else 1)
-bool wgrad3p_ok(const WgradArgs& a);
-hipError_t launch_wgrad3p(const WgradArgs& a, int splits, hipStream_t s, int nz);
-bool wgrad1p_ok(const WgradArgs& a);  // 96 -> 96 1x1 on k_wgrad1p (bf16x6)
-hipError_t launch_wgrad1p(const WgradArgs& a, int splits, hipStream_t s, bool up2 = false);
-bool wgrad1_ok(int mode, const WgradArgs& a);
-long wgrad_slab_floats(int mode, int N, int KH, int KW, int cin, int cout);
-int wgrad1_splits(int mode, int N, int KH, int KW);  // k_wgrad1 / k_wgrad1p split count
-hipError_t launch_wgrad1(int mode, const WgradArgs& a, float* dwb, hipStream_t s,
-                         RedBatch* rb = nullptr, bool x6 = false);
+// ---- weight-gradient launchers: one per kernel family, no decisions (wgrad_route.h) ----
+// Each maps the route onto its template instantiation and grid and sets the profiler label; a
+// route for another family, or one whose tile no instantiation has, is hipErrorInvalidValue.
+hipError_t launch_wgrad(const WgradArgs& a, const WgradRoute& r, hipStream_t s);    // k_wgrad
+hipError_t launch_wgrad3(const WgradArgs& a, const WgradRoute& r, hipStream_t s);   // k_wgrad3
+hipError_t launch_wgrad1(const WgradArgs& a, const WgradRoute& r, hipStream_t s);   // k_wgrad1
+hipError_t launch_wgrad3s(const WgradArgs& a, const WgradRoute& r, hipStream_t s);  // conv_x6.hip
+// k_wgrad3p / k_wgrad3q (wgrad_x6p.hip); decides a.slab_vec from the slab's alignment
+hipError_t launch_wgrad3p(const WgradArgs& a, const WgradRoute& r, hipStream_t s);
+hipError_t launch_wgrad1p(const WgradArgs& a, const WgradRoute& r, hipStream_t s);
 hipError_t launch_reduce_scatter(const float* slab, long slab_stride, int splits, long n,
                                  float* out, long grp, long ostride, long ooff, hipStream_t s,
                                  RedBatch* rb = nullptr);
 hipError_t launch_reduce(const float* slab, long slab_stride, int splits, long n, float* out,
                          hipStream_t s, RedBatch* rb = nullptr);
 bool fwd_supported(int gather, int nout);
-int gwgrad_splits(int mode, int N, int KH, int KW, int Cin, int Cout);
-bool gwgrad_ok(int mode, int Cin, int Cout, const View& g, const View& x);
-hipError_t launch_gwgrad(int mode, const WgradArgs& a, int splits, hipStream_t s);
-// the same 3x3 weight gradient on the bf16x6 kernel (conv_x6.hip)
-bool gwgrad_x6_ok(const WgradArgs& a);
-int gwgrad_x6_splits(const WgradArgs& a, int splits);
-hipError_t launch_gwgrad_x6(const WgradArgs& a, int splits, hipStream_t s);
-bool wgrad_supported(int mode, int cout, int cin);
 
 // ---- elementwise launchers (elementwise.hip) ----
 hipError_t launch_pool_fwd(const float* a, int N, int H, int W, int C, float* out, int os, int oo,

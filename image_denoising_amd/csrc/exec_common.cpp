@@ -165,36 +165,67 @@ hipError_t deconv_dgrad(const View& dy, int N, int h, int w, int cout, const flo
   return launch_fwd(G_DN2, a, s);
 }
 
-hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
-                 float* dwb, float* slab, int splits, hipStream_t s, bool x6, const float* zeros,
-                 RedBatch* rb, const WgradHead* head) {
+dn_status wgrad_run(const WgradRoute& r, const float* g, const float* x, float* dwb, float* slab,
+                    const float* zeros, hipStream_t s, RedBatch* rb, const WgradHead* head) {
+  const WgradShape& sh = r.sh;
+  if (r.kernel == WK_NONE || (head ? head->gnb : 0) != sh.head_gnb) {
+    set_error(r.err ? r.err : "weight-gradient route built for another head");
+    return DN_ERR_ARG;
+  }
+  const int mode = sh.mode, taps = wgrad_taps(mode), sp = r.splits;
   WgradArgs a{};
   if (head) {
     a.head_gnb = head->gnb; a.hd_dy = head->dy; a.hd_dy_stride = head->dy_stride;
     a.hd_wc = head->wc; a.hd_slab_c = head->slab_c; a.hd_dwc = head->dwc;
   }
-  a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
-  a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
-  a.N = N; a.KH = KH; a.KW = KW; a.Cout = cout; a.Cin = cin;
-  const int taps = mode == W_C3 ? 9 : (mode == W_UP2 ? 4 : 1);
-  const long n = (long)cout * cin * taps + cout;
-  const OpTimer timer(s, mode == W_C3 ? "wgrad3" : (mode == W_UP2 ? "wgrad_up" : "wgrad1"),
-                      2.0 * N * KH * KW * cout * cin * taps, cin, cout, KH, KW, N);
-  // slab scratch layout: [64 floats | splits x (W + b)]
+  a.g = g; a.g_stride = sh.g_stride; a.g_off = sh.g_off;
+  a.x = x; a.x_stride = sh.x_stride; a.x_off = sh.x_off;
+  a.N = sh.N; a.KH = sh.KH; a.KW = sh.KW; a.Cout = sh.Cout; a.Cin = sh.Cin;
+  // slab scratch layout: [64 floats | par x splits rows of (W + b)]
   a.zeros = zeros ? zeros : slab;
-  a.slab = slab + 64; a.slab_stride = n;
-  a.wlayout = mode == W_UP2 ? 1 : 0;
-  a.cin_total = cin; a.ci_base = 0; a.bias = 1;
-  if (!zeros) {
-    hipError_t e = hipMemsetAsync(slab, 0, 64 * sizeof(float), s);
-    if (e != hipSuccess) return e;
+  a.slab = slab + 64; a.slab_stride = r.row;
+  a.wlayout = mode == W_UP2 ? 1 : 0;  // deconv weight (in, out, 2, 2)
+  a.cin_total = sh.cin_total; a.ci_base = sh.ci_base; a.bias = sh.bias ? 1 : 0;
+  if (r.zc) { a.zc = r.zc; a.cout_total = sh.Cout; }  // all output-channel blocks in ONE launch
+  // (k_reduce_batch sets no label: the record keeps the GEMM kernel's)
+  const OpTimer timer(s, mode == W_C3 ? "wgrad3" : (mode == W_UP2 ? "wgrad_up" : "wgrad1"),
+                      2.0 * sh.N * sh.KH * sh.KW * sh.Cout * sh.Cin * taps, sh.Cin, sh.Cout, sh.KH,
+                      sh.KW, sh.N);
+  if (!zeros) DN_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s));
+  switch (r.kernel) {
+    case WK_WGRAD: DN_TRY(launch_wgrad(a, r, s)); break;
+    case WK_WGRAD3: DN_TRY(launch_wgrad3(a, r, s)); break;
+    case WK_WGRAD1: DN_TRY(launch_wgrad1(a, r, s)); break;
+    case WK_WGRAD3S: DN_TRY(launch_wgrad3s(a, r, s)); break;
+    case WK_WGRAD1P: DN_TRY(launch_wgrad1p(a, r, s)); break;
+    default: DN_TRY(launch_wgrad3p(a, r, s)); break;  // WK_WGRAD3P, WK_WGRAD3Q
   }
-  // 1x1 / deconv, own splits (x6: the 96 x 96 1x1 layers on k_wgrad1p)
-  if (wgrad1_ok(mode, a)) return launch_wgrad1(mode, a, dwb, s, rb, x6);
-  if (x6 && mode == W_C3) splits = wgrad_splits_x6(a, splits);
-  hipError_t e = launch_wgrad(mode, a, splits, s, x6);
-  if (e != hipSuccess) return e;
-  return launch_reduce(slab + 64, n, splits, n, dwb, s, rb);
+  // the reductions into dwb (PyTorch layout, the bias after the weight)
+  const long W = (long)sh.Cout * sh.Cin * taps, Wt = (long)sh.Cout * sh.cin_total * taps;
+  if (r.par == 4) {
+    // W[ci][co][a][b] in output order: element e = 4 (ci*Cout + co) + ab lives in parity ab's
+    // block of sp rows
+    RedJob j = red_job(a.slab, r.row, sp, W, dwb);
+    j.ig = 4; j.is1 = 1; j.is2 = (int)(sp * r.row);
+    DN_TRY(red_add(rb, j, s));
+    DN_TRY(launch_reduce(a.slab + W / 4, r.row, 4 * sp, sh.Cout, dwb + W, s, rb));  // bias: all rows
+    return DN_OK;
+  }
+  if (a.hd_slab_c) {  // nin_c's weight gradient formed by the same launch (k_wgrad1p GNB)
+    const long rc = (long)a.head_gnb * 96 + a.head_gnb;
+    DN_TRY(launch_reduce(a.hd_slab_c, rc, sp, rc, a.hd_dwc, s, rb));
+  }
+  if (sh.cin_total == sh.Cin) {
+    DN_TRY(launch_reduce(a.slab, r.row, sp, r.row, dwb, s, rb));
+    return DN_OK;
+  }
+  // an input-channel slice of a wider weight: W[co][ci_base + ci < Cin][t], then the bias
+  RedJob j = red_job(a.slab + (long)sh.ci_base * taps, r.row, sp, W, dwb + (long)sh.ci_base * taps);
+  j.ig = j.og = sh.Cin * taps;
+  j.is1 = j.os1 = sh.cin_total * taps;
+  DN_TRY(red_add(rb, j, s));  // (a full batch flushes on s, behind the weight gradients it reads)
+  if (sh.bias) DN_TRY(red_add(rb, red_job(a.slab + Wt, r.row, sp, sh.Cout, dwb + Wt), s));
+  return DN_OK;
 }
 
 // ---- the UNet's and the RESNET's common pieces ----
@@ -206,18 +237,23 @@ WgradSlab plan_wgrad_slab(int kind, int mode, int N, int KH, int KW, const Layer
       r.splits = enc0_wgrad_splits(N, KH, KW);
       r.floats = r.splits * row;
       break;
-    case SLAB_D1A:  // split count of the MFMA kernel's slice; the thin kernel's rows hold [co][C][9]
-      r.splits = wgrad_splits(mode, N, KH, KW, L.cin - C, L.cout);
+    case SLAB_D1A:  // the MFMA kernel's slice in rows of the whole weight; the thin kernel's rows hold [co][C][9]
+      r.splits = wgrad_size(mode, N, KH, KW, L.cin - C, L.cout, false).rows;
       r.floats = r.splits * row + (long)enc0_wgrad_splits(N, KH, KW) * L.cout * C * 9;
       break;
-    case SLAB_NINC_THIN:
+    case SLAB_NINC_THIN: {  // ... or as many rows as nin_b's k_wgrad1p<., GNB> launch has splits
+      WgradShape nb = wgrad_shape(W_C1, N, KH, KW, 96, 96, 96, 0, 96, 0, true);
+      nb.head_gnb = 1;
       r.splits = wgrad_thin_splits((long)N * KH * KW);
-      r.floats = std::max<long>(r.splits, wgrad1_splits(W_C1, N, KH, KW)) * row;
+      r.floats = std::max(r.splits, wgrad_route(nb).splits) * row;
       break;
-    default:
-      r.splits = wgrad_splits(mode, N, KH, KW, L.cin, L.cout);
-      r.floats = wgrad_slab_floats(mode, N, KH, KW, L.cin, L.cout);
+    }
+    default: {
+      const WgradSize z = wgrad_size(mode, N, KH, KW, L.cin, L.cout, false);
+      r.splits = z.rows;
+      r.floats = z.floats;
       break;
+    }
   }
   return r;
 }
@@ -298,8 +334,7 @@ dn_status head_backward(BwdStreams& bs, const TailShape& t, HeadBwdArgs h, bool 
                         const WgradDst& nina, const WgradDst& ninb, const WgradDst& ninc) {
   const int N = t.N, H = t.H, W = t.W, OC = h.oc;
   const hipStream_t s2 = bs.s2;
-  auto V = [](const float* p, int stride) { return View{const_cast<float*>(p), stride, 0}; };
-  const View g_nb = V(h.g_nb, 96);
+  const float* g_nb = h.g_nb;
   // (head_x6: nin_b's weight gradient recomputes g_nb, nothing reads a stored one)
   if (head_x6) h.g_nb = nullptr;
   DN_TIMED(bs.s, "head_bwd", 2.0 * h.npx * 96 * (2 * 96 + OC), OC, 96, H, W, N,
@@ -307,23 +342,28 @@ dn_status head_backward(BwdStreams& bs, const TailShape& t, HeadBwdArgs h, bool 
   const bool fold_c = head_x6 && OC == 1;  // nin_c's weight gradient inside nin_b's (k_wgrad1p)
   if (!fold_c) {
     DN_TRY(bs.fork());
-    if (OC <= 4)
+    if (OC <= 4) {
       DN_TIMED(s2, "wgrad1", 2.0 * h.npx * 96 * OC, 96, OC, H, W, N,
                launch_wgrad_thin(h.dy, h.dy_stride, OC, h.nb, h.npx, ninc.slab + 64, ninc.splits,
                                  ninc.dwb, s2, &bs.rb));
-    else
-      DN_TRY(wgrad(W_C1, V(h.dy, h.dy_stride), V(h.nb, 96), N, H, W, OC, 96, ninc.dwb, ninc.slab,
-                   ninc.splits, s2, false, t.zeros, &bs.rb));
+    } else {
+      const WgradShape nc = wgrad_shape(W_C1, N, H, W, 96, OC, h.dy_stride, 0, 96, 0);
+      if (dn_status st = wgrad_run(wgrad_route(nc), h.dy, h.nb, ninc.dwb, ninc.slab, t.zeros, s2,
+                                   &bs.rb))
+        return st;
+    }
   }
   DN_TRY(bs.fork());
   const WgradHead hd{head_x6 ? OC : 0, h.dy, h.dy_stride, h.wc,
                      fold_c ? ninc.slab + 64 : nullptr, ninc.dwb};
-  DN_TRY(wgrad(W_C1, head_x6 ? V(h.nb, 96) : g_nb, V(h.na, 96), N, H, W, 96, 96, ninb.dwb,
-               ninb.slab, ninb.splits, s2, t.x6, t.zeros, &bs.rb, &hd));
+  WgradShape nin = wgrad_shape(W_C1, N, H, W, 96, 96, 96, 0, 96, 0, t.x6);
+  const WgradRoute r_a = wgrad_route(nin);
+  nin.head_gnb = hd.gnb;
+  if (dn_status st = wgrad_run(wgrad_route(nin), head_x6 ? h.nb : g_nb, h.na, ninb.dwb, ninb.slab,
+                               t.zeros, s2, &bs.rb, &hd))
+    return st;
   DN_TRY(bs.fork());
-  DN_TRY(wgrad(W_C1, V(h.g_na, 96), V(h.d1b, 96), N, H, W, 96, 96, nina.dwb, nina.slab,
-               nina.splits, s2, t.x6, t.zeros, &bs.rb));
-  return DN_OK;
+  return wgrad_run(r_a, h.g_na, h.d1b, nina.dwb, nina.slab, t.zeros, s2, &bs.rb);
 }
 
 dn_status d1a_wgrad(BwdStreams& bs, const TailShape& t, const float* g_d1a, const View& c1,
@@ -332,21 +372,11 @@ dn_status d1a_wgrad(BwdStreams& bs, const TailShape& t, const float* g_d1a, cons
   const hipStream_t s2 = bs.s2;
   const long n = (long)96 * c1k * 9 + 96;
   float* slab = d.slab + 64;
-  WgradArgs a{};
-  a.g = g_d1a; a.g_stride = 96; a.g_off = 0;
-  a.x = c1.p; a.x_stride = c1.stride; a.x_off = c1.off;
-  a.N = N; a.KH = H; a.KW = W; a.Cout = 96; a.Cin = up;
-  a.zeros = t.zeros; a.slab = slab; a.slab_stride = n;
-  a.wlayout = 0; a.cin_total = c1k; a.ci_base = 0; a.bias = 1;
-  const int sp = t.x6 ? wgrad_splits_x6(a, d.splits) : d.splits;
+  WgradShape sh = wgrad_shape(W_C3, N, H, W, up, 96, 96, 0, c1.stride, c1.off, t.x6);
+  sh.cin_total = c1k;  // rows of W[co][c1k][9]; the reduction takes this launch's columns
   DN_TRY(bs.fork());
-  DN_TIMED(s2, "wgrad3", 2.0 * N * H * W * 96 * up * 9, up, 96, H, W, N,
-           launch_wgrad(W_C3, a, sp, s2, t.x6));
-  RedJob j = red_job(slab, n, sp, 96L * up * 9, d.dwb);  // W[co][ci < up][t]
-  j.ig = j.og = up * 9;
-  j.is1 = j.os1 = c1k * 9;
-  DN_TRY(red_add(&bs.rb, j, s2));  // (a full batch flushes on s2, behind the wgrads it reads)
-  DN_TRY(red_add(&bs.rb, red_job(slab + 96L * c1k * 9, n, sp, 96, d.dwb + 96L * c1k * 9), s2));
+  if (dn_status st = wgrad_run(wgrad_route(sh), g_d1a, c1.p, d.dwb, d.slab, t.zeros, s2, &bs.rb))
+    return st;
   // input-channel slice: compact [co][C][9] rows after the MFMA kernel's, own split count,
   // scattered into W[co][up + ci][t]
   float* thin = slab + (long)d.splits * n;

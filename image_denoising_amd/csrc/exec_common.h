@@ -100,18 +100,25 @@ struct WgradHead {
   int gnb; const float* dy; int dy_stride; const float* wc;
   float* slab_c; float* dwc;
 };
-// slab: [64 floats | splits x (W + b)]; zeros == nullptr: the 64 floats are zeroed here and
-// serve as the DMA padding; rb: the reduction is queued, not launched
-hipError_t wgrad(int mode, const View& g, const View& x, int N, int KH, int KW, int cout, int cin,
-                 float* dwb, float* slab, int splits, hipStream_t s, bool x6 = false,
-                 const float* zeros = nullptr, RedBatch* rb = nullptr,
-                 const WgradHead* head = nullptr);
+// The one weight-gradient launch sequence: fills WgradArgs from the route and the operand
+// pointers (g, x: the origins of the route's views), takes the launch profiler's record, launches
+// the route's kernel and queues its reductions into dwb = [W | b].  slab: [64 floats | the route's
+// rows]; zeros == nullptr: the 64 floats are zeroed here and serve as the DMA padding; rb: the
+// reductions are queued, not launched.  A route without a kernel is DN_ERR_ARG with its reason.
+dn_status wgrad_run(const WgradRoute& r, const float* g, const float* x, float* dwb, float* slab,
+                    const float* zeros, hipStream_t s, RedBatch* rb = nullptr,
+                    const WgradHead* head = nullptr);
+// the route of the fixed family's usual launch from its two views
+inline WgradRoute wgrad_route(int mode, const View& g, const View& x, int N, int KH, int KW,
+                              int cout, int cin, bool x6) {
+  return wgrad_route(wgrad_shape(mode, N, KH, KW, cin, cout, g.stride, g.off, x.stride, x.off, x6));
+}
 
 // ---- the UNet's and the RESNET's common pieces ----
 // One layer's weight-gradient slab of a with-backward plan: its split count and the floats behind
 // the slab's 64 leading ones.  KH x KW: the grid its weight gradient runs over; C: in_nc.
 enum SlabKind {
-  SLAB_CONV,       // wgrad(): 3x3, 1x1 or deconv (mode W_C3 / W_C1 / W_UP2)
+  SLAB_CONV,       // wgrad_run(): 3x3, 1x1 or deconv (mode W_C3 / W_C1 / W_UP2)
   SLAB_ENC0,       // launch_enc0_wgrad
   SLAB_D1A,        // d1a_wgrad: the MFMA kernel's rows, then the thin kernel's input-slice rows
   SLAB_NINC_THIN,  // launch_wgrad_thin, or the rows nin_b's k_wgrad1p<., GNB> writes for nin_c
@@ -154,7 +161,7 @@ dn_status head_forward(const HeadArgs& h, const float* d1b, int N, int H, int W,
 
 // the full-resolution tail of a backward pass; x6: weight gradients in the bf16x6 arithmetic
 struct TailShape { int N, H, W; bool x6; const float* zeros; };
-// a layer's [W | b] range of dparams, its slab and its planned split count
+// a layer's [W | b] range of dparams, its slab and the rows its plan reserved (plan_wgrad_slab)
 struct WgradDst { float* dwb; float* slab; int splits; };
 // The head's backward: nin_c -> nin_b -> nin_a data gradients in one kernel (g_nb, g_na, g_d1b),
 // then the three 1x1 weight gradients, each forked.  h: the network's buffers, image and NHWC dy.

@@ -209,39 +209,6 @@ dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G
   return DN_OK;
 }
 
-// every layer's slab rows hold [W ; b] (the bias row is there whether the layer has one or not)
-long gwgrad_slab_floats(int mode, int N, int h, int w, int cin, int cout) {
-  const int taps = mode == W_C3 ? 9 : 1;
-  return (long)gwgrad_splits(mode, N, h, w, cin, cout) * ((long)cout * cin * taps + cout);
-}
-
-dn_status gwgrad_run(int mode, const View& g, const View& x, int N, int h, int w, int cin,
-                     int cout, bool bias, int prec, float* dwb, float* slab, hipStream_t s) {
-  if (!gwgrad_ok(mode, cin, cout, g, x)) {
-    set_error("no blocked weight-gradient kernel for this layer shape or these views");
-    return DN_ERR_ARG;
-  }
-  const int taps = mode == W_C3 ? 9 : 1;
-  const long n = (long)cout * cin * taps + (bias ? cout : 0);
-  WgradArgs a{};
-  a.g = g.p; a.g_stride = g.stride; a.g_off = g.off;
-  a.x = x.p; a.x_stride = x.stride; a.x_off = x.off;
-  a.N = N; a.KH = h; a.KW = w; a.Cout = cout; a.Cin = cin;
-  a.zeros = slab; a.slab = slab + 64; a.slab_stride = n;
-  a.wlayout = 0; a.cin_total = cin; a.ci_base = 0; a.bias = bias ? 1 : 0;
-  int sp = gwgrad_splits(mode, N, h, w, cin, cout);
-  DN_TRY(hipMemsetAsync(slab, 0, 64 * sizeof(float), s));
-  // fp32_x6: the 3x3 weight gradients on the bf16x6 kernel too
-  if (prec == DN_PREC_FP32_X6 && mode == W_C3 && gwgrad_x6_ok(a)) {
-    sp = gwgrad_x6_splits(a, sp);
-    DN_TRY(launch_gwgrad_x6(a, sp, s));
-  } else {
-    DN_TRY(launch_gwgrad(mode, a, sp, s));
-  }
-  DN_TRY(launch_reduce(slab + 64, n, sp, n, dwb, s));
-  return DN_OK;
-}
-
 bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err) {
   if (c.in_nc < 1 || c.in_nc > 3 || c.out_nc < 1 || c.out_nc > 4) {
     err = "ImprovedUNet: in_nc must be 1..3 and out_nc 1..4";
@@ -453,7 +420,7 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
     if (s.out.o >= 0) fsum += slot_floats(s.L.k, s.L.cin, s.L.cout);
     if (s.nout) bsum += slot_floats(s.L.k, s.L.cout, s.nout);
     if (s.wmode >= 0)
-      slab = std::max(slab, gwgrad_slab_floats(s.wmode, N, H >> s.lvl, W >> s.lvl, s.L.cin, s.L.cout));
+      slab = std::max(slab, wgrad_size(s.wmode, N, H >> s.lvl, W >> s.lvl, s.L.cin, s.L.cout, true).floats);
   }
   p.pack_floats = std::max(fsum, bsum);
   p.pack = allocf(p.pack_floats);
@@ -593,16 +560,19 @@ dn_status wgrad_g(const Ctx& c, float* dprm, const IConv& L) {
   // on the side stream, behind the main stream's work so far (g is its latest output)
   const hipStream_t s2 = c.bs->s2;
   DN_TRY(c.bs->fork());
-  const OpTimer timer(s2, L.k == 3 ? "wgrad3" : "wgrad1", conv_flops(N, h, w, L.cout, L.cin, L.k),
-                      L.cin, L.cout, h, w, N);
-  const int taps = s.wmode == W_C3 ? 9 : 1;
   const bool bias = L.b >= 0;
-  if (bias && L.b != L.w + (long)L.cout * L.cin * taps) {
+  if (bias && L.b != L.w + (long)L.cout * L.cin * wgrad_taps(s.wmode)) {
     set_error("ImprovedUNet: bias does not follow its weight");
     return DN_ERR_ARG;
   }
-  return gwgrad_run(s.wmode, c.V(s.g), c.V(s.in), N, h, w, L.cin, L.cout, bias, c.prec,
-                    dprm + L.w, c.ws + c.p.slab, s2);
+  // the blocked family (any Cout in output-channel blocks, views with a channel offset); the one
+  // slab serves every layer in turn, so each reduction is launched behind its weight gradient
+  const View g = c.V(s.g), x = c.V(s.in);
+  WgradShape sh = wgrad_shape(s.wmode, N, h, w, L.cin, L.cout, g.stride, g.off, x.stride, x.off,
+                              c.prec == DN_PREC_FP32_X6);
+  sh.blocked = true;
+  sh.bias = bias;
+  return wgrad_run(wgrad_route(sh), g.p, x.p, dprm + L.w, c.ws + c.p.slab, nullptr, s2);
 }
 
 dn_status gn_fwd(const Ctx& c, const IGN& g, const View& z, int h, int w, float* stats, int act,

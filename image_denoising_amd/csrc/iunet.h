@@ -95,15 +95,6 @@ dn_status gn_forward(const View& z, int N, long P, int C, int G, const float* ga
 dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G,
                       const float* gamma, const float* stats, const View& dz, float* dgamma,
                       float* dbeta, double* part, float* ca, float* cb, float* cc, hipStream_t s);
-// The blocked weight gradient (mode W_C3 / W_C1, any Cout in output-channel blocks over
-// blockIdx.z, views with a channel offset): dwb = [W (cout, cin, k, k) | b (cout) if bias] from
-// g = dL/d(conv output) and the conv's input x.  slab: 64 floats (zeroed here, the kernels' padding
-// source) followed by gwgrad_slab_floats(); prec DN_PREC_FP32_X6 takes the bf16x6 kernels where
-// gwgrad_x6_ok.
-long gwgrad_slab_floats(int mode, int N, int h, int w, int cin, int cout);
-dn_status gwgrad_run(int mode, const View& g, const View& x, int N, int h, int w, int cin,
-                     int cout, bool bias, int prec, float* dwb, float* slab, hipStream_t s);
-
 bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err);
 bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan& p,
                       std::string& err);

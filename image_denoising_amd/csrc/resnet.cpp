@@ -312,13 +312,12 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
   auto dgrad = [&](int i, const View& dz, const View& mask, const View& dxv) -> hipError_t {
     return run_dgrad(B.r[i], ws, dz, N, H, W, p.P.L[i], res_dgrad_nout(p, i), EPI_MASK, mask, dxv, s);
   };
-  // layer i's weight gradient on the side stream, behind the main stream's work so far
-  auto wg = [&](int i, const View& g, const View& xv) -> hipError_t {
+  // layer i's weight gradient; side: on the side stream, behind the main stream's work so far
+  auto wg = [&](int i, const View& g, const View& xv, bool side = true) -> dn_status {
     const Layer& L = p.P.L[i];
-    hipError_t e = bs.fork();
-    if (e != hipSuccess) return e;
-    return wgrad(L.k == 3 ? W_C3 : W_C1, g, xv, N, H, W, L.cout, L.cin, G(i), SL(i), p.splits[i], bs.s2,
-                 x6, Z, &bs.rb);
+    if (side) DN_TRY(bs.fork());
+    return wgrad_run(wgrad_route(L.k == 3 ? W_C3 : W_C1, g, xv, N, H, W, L.cout, L.cin, x6), g.p,
+                     xv.p, G(i), SL(i), Z, side ? bs.s2 : s, &bs.rb);
   };
 
   // dy arrives NCHW; out_nc == 1: that is NHWC
@@ -338,7 +337,7 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
     if (dn_status st = head_backward(bs, tail, h, B.head_x6, dst(R_NINA), dst(R_NINB), dst(R_NINC)))
       return st;
   }
-  DN_TRY(wg(R_D1B, V(p.g_d1b, 96), V(p.d1a, 96)));
+  if (dn_status st_ = wg(R_D1B, V(p.g_d1b, 96), V(p.d1a, 96))) return st_;
   DN_TRY(dgrad(R_D1B, V(p.g_d1b, 96), V(p.d1a, 96), V(p.g_d1a, 96)));
   // dec_conv1a's weight gradient: [d2b]'s channels and the network input's (as the UNet's)
   if (dn_status st = d1a_wgrad(bs, tail, ws + p.g_d1a, V(p.c1, p.c1s), p.c1k, ws + p.xin, C, dst(R_D1A)))
@@ -348,22 +347,22 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
   View g = V(p.g_c1, 2 * nf);  // pre-activation gradient of dec_conv{k}b's output
   for (int k = 2; k <= 5; ++k) {
     const int ia = res_da(k), ib = ia + 1;
-    DN_TRY(wg(ib, g, V(p.da[k], 2 * nf)));
+    if (dn_status st_ = wg(ib, g, V(p.da[k], 2 * nf))) return st_;
     DN_TRY(dgrad(ib, g, V(p.da[k], 2 * nf), V(p.g_da[k], 2 * nf)));
-    DN_TRY(wg(ia, V(p.g_da[k], 2 * nf), V(p.c[k], p.cs[k])));
+    if (dn_status st_ = wg(ia, V(p.g_da[k], 2 * nf), V(p.c[k], p.cs[k]))) return st_;
     // the concat buffer masks both parts: [dec_conv{k+1}b | a_{k-1}] ([a6 | a4] at k = 5)
     DN_TRY(dgrad(ia, V(p.g_da[k], 2 * nf), V(p.c[k], p.cs[k]), V(p.g_c[k], p.cs[k])));
     g = V(p.g_c[k], p.cs[k], 0);
   }
   DN_TRY(bs.flush_reductions());
   // enc_conv6 (input a5), then enc_conv5 .. enc_conv2 (input a_j = the skip slice of c_{j+1})
-  DN_TRY(wg(R_ENC6, V(p.g_c[5], p.cs[5], 0), V(p.a5, nf)));
+  if (dn_status st_ = wg(R_ENC6, V(p.g_c[5], p.cs[5], 0), V(p.a5, nf))) return st_;
   DN_TRY(dgrad(R_ENC6, V(p.g_c[5], p.cs[5], 0), V(p.a5, nf), V(p.g_a5, nf)));
   View ge = V(p.g_a5, nf);  // pre-activation gradient of enc_conv{j+1}'s output
   for (int j = 4; j >= 1; --j) {
     const int i = R_ENC0 + j + 1, k = j + 1, so = (k == 5) ? nf : 2 * nf;
     const View aj = V(p.c[k], p.cs[k], so);
-    DN_TRY(wg(i, ge, aj));
+    if (dn_status st_ = wg(i, ge, aj)) return st_;
     DN_TRY(dgrad(i, ge, aj, V(p.g_t, nf)));
     DN_TIMED(s, "accumulate", 0, nf, nf, H, W, N,
              launch_add_slice(ws + p.g_c[k], p.cs[k], so, ws + p.g_t, nf, px, ws + p.g_a[j], s));
@@ -376,8 +375,7 @@ dn_status resnet_backward(const ResPlan& p, const float* prm, const float* dy, f
   DN_TIMED(bs.s2, "wgrad3_thin", 2.0 * px * nf * C * 9, C, nf, H, W, N,
            launch_enc0_wgrad(ws + p.g_a0, nf, ws + p.xin, N, C, H, W, SL(R_ENC0) + 64,
                              p.splits[R_ENC0], G(R_ENC0), bs.s2, &bs.rb));
-  DN_TRY(wgrad(W_C3, ge, V(p.a0, nf), N, H, W, nf, nf, G(R_ENC1), SL(R_ENC1), p.splits[R_ENC1], s,
-               x6, Z, &bs.rb));
+  if (dn_status st_ = wg(R_ENC1, ge, V(p.a0, nf), false)) return st_;
   // up5.deconv is never used: an exact zero gradient (dparams is overwritten, not accumulated)
   DN_TRY(hipMemsetAsync(G(R_UP5), 0, (p.P.L[R_UP5].wcount + p.P.L[R_UP5].cout) * sizeof(float), s));
   DN_TRY(bs.join());

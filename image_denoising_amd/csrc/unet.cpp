@@ -222,7 +222,7 @@ bool build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, Plan& p, st
       int KH = H >> lvl, KW = W >> lvl;
       int mode = L.deconv ? W_UP2 : (L.k == 3 ? W_C3 : W_C1);
       if (L.deconv) { KH = H >> (lvl + 1); KW = W >> (lvl + 1); }
-      // (nin_c above 4 outputs goes through wgrad() like any 1x1 layer)
+      // (nin_c above 4 outputs goes through wgrad_run() like any 1x1 layer)
       const int kind = i == ENC0 ? SLAB_ENC0 : i == D1A ? SLAB_D1A
                        : (i == NINC && p.OC <= 4) ? SLAB_NINC_THIN : SLAB_CONV;
       const WgradSlab sl = plan_wgrad_slab(kind, mode, N, KH, KW, L, p.C);
@@ -710,6 +710,12 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   const float* Z = ws + p.zeros;
   auto SL = [&](int i) { return ws + p.slab[i]; };
   auto dst = [&](int i) { return WgradDst{G(i), SL(i), p.splits[i]}; };
+  // layer i's weight gradient on stream st: g (cout channels) against xv (cin channels), level l
+  auto wg = [&](int i, int mode, const View& g, const View& xv, int l, int cout, int cin, bool x6_,
+                hipStream_t st) -> dn_status {
+    return wgrad_run(wgrad_route(mode, g, xv, N, H(l), Wd(l), cout, cin, x6_), g.p, xv.p, G(i),
+                     SL(i), Z, st, &bs.rb);
+  };
   // layer i: dz (the layer's cout channels) -> dx, channels [0, dgrad_nout(p, i)) of its input
   auto conv_dgrad = [&](int i, const View& dz, int epi, const View& mask, const View& dx,
                         hipStream_t st) -> hipError_t {
@@ -737,8 +743,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     if (dn_status st = head_backward(bs, tail, h, B.head_x6, dst(NINA), dst(NINB), dst(NINC))) return st;
   }
   DN_TRY(bs.fork());
-  DN_TRY(wgrad(W_C3, V(p.g_d1b, 96), V(p.d1a, 96), N, H(0), Wd(0), 96, 96, G(D1B), SL(D1B),
-               p.splits[D1B], bs.s2, x6, Z, &bs.rb));
+  if (dn_status st_ = wg(D1B, W_C3, V(p.g_d1b, 96), V(p.d1a, 96), 0, 96, 96, x6, bs.s2)) return st_;
   DN_TRY(conv_dgrad(D1B, V(p.g_d1b, 96), EPI_MASK, V(p.d1a, 96), V(p.g_d1a, 96), s));
   // dec_conv1a's weight gradient: up1's channels [0, 2nf) and the network input's [2nf, 2nf + C)
   if (dn_status st = d1a_wgrad(bs, tail, ws + p.g_d1a, V(p.c1, p.c1s), p.c1k, ws + p.xin, C, dst(D1A)))
@@ -754,20 +759,20 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     const int iu = up_idx[l - 1];  // deconv producing level l-1 from level l
     // deconv wgrad: x = d_l b (level l), dU at level l-1
     DN_TRY(bs.fork());
-    DN_TRY(wgrad(W_UP2, dU, V(p.db[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf, G(iu), SL(iu),
-                 p.splits[iu], bs.s2, x6, Z, &bs.rb));
+    if (dn_status st_ = wg(iu, W_UP2, dU, V(p.db[l], 2 * nf), l, 2 * nf, 2 * nf, x6, bs.s2))
+      return st_;
     DN_TRY(deconv_dgrad(iu, dU, V(p.db[l], 2 * nf), EPI_MASK, V(p.g_db[l], 2 * nf), s));
     const int ia = da_idx[l], ib = ia + 1;
     DN_TRY(bs.fork());
-    DN_TRY(wgrad(W_C3, V(p.g_db[l], 2 * nf), V(p.da[l], 2 * nf), N, H(l), Wd(l), 2 * nf, 2 * nf,
-                 G(ib), SL(ib), p.splits[ib], bs.s2, x6, Z, &bs.rb));
+    if (dn_status st_ = wg(ib, W_C3, V(p.g_db[l], 2 * nf), V(p.da[l], 2 * nf), l, 2 * nf, 2 * nf, x6, bs.s2))
+      return st_;
     DN_TRY(conv_dgrad(ib, V(p.g_db[l], 2 * nf), EPI_MASK, V(p.da[l], 2 * nf), V(p.g_da[l], 2 * nf),
                       s));
     DN_TRY(bs.fork());
     // channel count ck (the layer's cin, what G(ia) and the dgrad pack are sized for); cs is
     // only the pixel stride (larger under a DN_C1S_ALIGN override)
-    DN_TRY(wgrad(W_C3, V(p.g_da[l], 2 * nf), V(p.c[l], p.cs[l]), N, H(l), Wd(l), 2 * nf, p.ck[l],
-                 G(ia), SL(ia), p.splits[ia], bs.s2, x6, Z, &bs.rb));
+    if (dn_status st_ = wg(ia, W_C3, V(p.g_da[l], 2 * nf), V(p.c[l], p.cs[l]), l, 2 * nf, p.ck[l], x6, bs.s2))
+      return st_;
     DN_TRY(conv_dgrad(ia, V(p.g_da[l], 2 * nf), EPI_PLAIN, none, V(p.g_c[l], p.cs[l]), s));
     dU = V(p.g_c[l], p.cs[l], 0);  // [u_{l+1} grad | skip grad]
   }
@@ -780,13 +785,12 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   }
   // up5: x = a6 (level 5), dU = g_c5[0:nf]
   DN_TRY(bs.fork());
-  DN_TRY(wgrad(W_UP2, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), N, H(5), Wd(5), nf, nf, G(UP5), SL(UP5),
-               p.splits[UP5], bs.s2, false, Z, &bs.rb));
+  if (dn_status st_ = wg(UP5, W_UP2, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), 5, nf, nf, false, bs.s2))
+    return st_;
   DN_TRY(deconv_dgrad(UP5, V(p.g_c[4], p.cs[4], 0), V(p.a6, nf), EPI_MASK, V(p.g_a6, nf), s));
   // enc_conv6 (input p5, level 5)
   DN_TRY(bs.fork());
-  DN_TRY(wgrad(W_C3, V(p.g_a6, nf), V(p.p5, nf), N, H(5), Wd(5), nf, nf, G(ENC6), SL(ENC6),
-               p.splits[ENC6], bs.s2, x6, Z, &bs.rb));
+  if (dn_status st_ = wg(ENC6, W_C3, V(p.g_a6, nf), V(p.p5, nf), 5, nf, nf, x6, bs.s2)) return st_;
   DN_TRY(conv_dgrad(ENC6, V(p.g_a6, nf), EPI_PLAIN, none, V(p.g_p5, nf), s));
   // pool5 backward -> g_a5 (level 4)
   DN_TIMED(s, "pool_bwd", 0, 0, 0, 0, 0, 0, launch_pool_bwd(ws + p.a[4], N, H(4), Wd(4), nf, ws + p.g_p5, nf, 0, 1, ws + p.g_a[4], s));
@@ -795,8 +799,8 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
     const int li = ENC2 + (l - 1);
     const int skip = (l == 4) ? nf : 2 * nf;
     DN_TRY(bs.fork());
-    DN_TRY(wgrad(W_C3, V(p.g_a[l], nf), V(p.c[l], p.cs[l], skip), N, H(l), Wd(l), nf, nf, G(li),
-                 SL(li), p.splits[li], bs.s2, x6, Z, &bs.rb));
+    if (dn_status st_ = wg(li, W_C3, V(p.g_a[l], nf), V(p.c[l], p.cs[l], skip), l, nf, nf, x6, bs.s2))
+      return st_;
     DN_TRY(conv_dgrad(li, V(p.g_a[l], nf), EPI_ACCUM, none, V(p.g_c[l], p.cs[l], skip), s));
     // pool_l backward: d p_l (skip slice) -> gradient of the level l-1 activation
     if (l > 1) {
@@ -821,8 +825,7 @@ dn_status unet_backward(const Plan& p, const float* prm, const float* dy, float*
   DN_TIMED(bs.s2, "wgrad3_thin", 2.0 * N * H(0) * Wd(0) * nf * C * 9, C, nf, H(0), Wd(0), N,
            launch_enc0_wgrad(ws + p.g_a0, nf, ws + p.xin, N, C, H(0), Wd(0), SL(ENC0) + 64,
                              p.splits[ENC0], G(ENC0), bs.s2, &bs.rb));
-  DN_TRY(wgrad(W_C3, V(p.g_a1, nf), V(p.a0, nf), N, H(0), Wd(0), nf, nf, G(ENC1), SL(ENC1),
-               p.splits[ENC1], s, x6, Z, &bs.rb));
+  if (dn_status st_ = wg(ENC1, W_C3, V(p.g_a1, nf), V(p.a0, nf), 0, nf, nf, x6, s)) return st_;
   DN_TRY(bs.join());  // the weight-gradient and reduction branches, before the last reduction
   DN_TIMED(s, "reduce", 0, 0, 0, 0, 0, 0, red_flush(bs.rb, s));
   if (tail_ready) DN_TRY(hipEventRecord(tail_ready, s));  // one stream: everything is final here

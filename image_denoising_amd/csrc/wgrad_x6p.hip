@@ -731,16 +731,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad3q(WgradArgs a) {
   }
 }
 
-// 96 output channels (or 96-channel blocks, a.zc == 96), 32 input channels per workgroup,
-// 16-byte aligned NHWC views, images under 2 GiB per operand (32-bit buffer offsets)
-bool wgrad3p_ok(const WgradArgs& a) {
-  if ((a.zc ? a.zc != 96 : (a.Cout != 96 && a.Cout != 48)) || a.Cin < 32 || a.KW < 8) return false;
-  if ((a.g_stride | a.g_off | a.x_stride | a.x_off) & 3) return false;
-  if (a.x_off + ((a.Cin + 3) & ~3) > a.x_stride) return false;
-  return (long)a.KH * a.KW * a.g_stride * 4 < 0x7fffffffL &&
-         (long)a.KH * a.KW * a.x_stride * 4 < 0x7fffffffL;
-}
-
 // Stage rows of at most 16 pixels (2 rows of 16: 72 X pixels per stage instead of 102 for one
 // row of 32) and the late G split measured best (profiles/r4_wgp2_ab.log).  The encoder's
 // 48 -> 48 layers take the 4-wave k_wgrad3q at 128^2 (0.35-0.36 -> 0.31-0.33 ms); below that
@@ -761,31 +751,29 @@ static bool slab_vec_ok(const WgradArgs& a) {
   return (a.slab_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(a.slab) & 15) == 0;
 }
 
-hipError_t launch_wgrad3p(const WgradArgs& a0, int splits, hipStream_t s, int nz) {
-  if (!wgrad3p_ok(a0)) return hipErrorInvalidValue;
+hipError_t launch_wgrad3p(const WgradArgs& a0, const WgradRoute& r, hipStream_t s) {
+  const bool q = r.kernel == WK_WGRAD3Q;
+  if ((!q && r.kernel != WK_WGRAD3P) || (r.swl != 3 && r.swl != 4)) return hipErrorInvalidValue;
   WgradArgs a = a0;
   a.slab_vec = slab_vec_ok(a0) ? 1 : 0;
-  if (!a.zc && a.Cout == 48) {
-    const dim3 grid(splits, (a.Cin + 47) / 48, nz);
-    if (a.KW >= 128) {
-      prof_kernel(a.slab_vec ? "k_wgrad3q<4>" : "k_wgrad3q<4> dword");
-      hipLaunchKernelGGL(k_wgrad3q<4>, grid, dim3(256), 0, s, a);
-    } else if (a.KW >= 16) {
-      prof_kernel(a.slab_vec ? "k_wgrad3p<4,48>" : "k_wgrad3p<4,48> dword");
-      hipLaunchKernelGGL((k_wgrad3p<4, 48>), grid, dim3(192), 0, s, a);
-    } else {
-      prof_kernel(a.slab_vec ? "k_wgrad3p<3,48>" : "k_wgrad3p<3,48> dword");
-      hipLaunchKernelGGL((k_wgrad3p<3, 48>), grid, dim3(192), 0, s, a);
-    }
-    return hipGetLastError();
-  }
-  const dim3 grid(splits, (a.Cin + 31) / 32, nz), block(256);
-  if (a.KW >= 16) {
+  const dim3 grid(r.splits, (a.Cin + r.cib - 1) / r.cib, r.nz);
+  if (q && r.cib == 48 && r.swl == 4) {
+    prof_kernel(a.slab_vec ? "k_wgrad3q<4>" : "k_wgrad3q<4> dword");
+    hipLaunchKernelGGL(k_wgrad3q<4>, grid, dim3(256), 0, s, a);
+  } else if (!q && r.co_fr == 3 && r.cib == 48 && r.swl == 4) {
+    prof_kernel(a.slab_vec ? "k_wgrad3p<4,48>" : "k_wgrad3p<4,48> dword");
+    hipLaunchKernelGGL((k_wgrad3p<4, 48>), grid, dim3(192), 0, s, a);
+  } else if (!q && r.co_fr == 3 && r.cib == 48) {
+    prof_kernel(a.slab_vec ? "k_wgrad3p<3,48>" : "k_wgrad3p<3,48> dword");
+    hipLaunchKernelGGL((k_wgrad3p<3, 48>), grid, dim3(192), 0, s, a);
+  } else if (!q && r.co_fr == 6 && r.cib == 32 && r.swl == 4) {
     prof_kernel(a.slab_vec ? "k_wgrad3p<4,96>" : "k_wgrad3p<4,96> dword");
-    hipLaunchKernelGGL((k_wgrad3p<4>), grid, block, 0, s, a);
-  } else {
+    hipLaunchKernelGGL((k_wgrad3p<4>), grid, dim3(256), 0, s, a);
+  } else if (!q && r.co_fr == 6 && r.cib == 32) {
     prof_kernel(a.slab_vec ? "k_wgrad3p<3,96>" : "k_wgrad3p<3,96> dword");
-    hipLaunchKernelGGL((k_wgrad3p<3>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((k_wgrad3p<3>), grid, dim3(256), 0, s, a);
+  } else {
+    return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
@@ -1077,29 +1065,20 @@ __global__ __launch_bounds__(256, 2) void k_wgrad1p(WgradArgs a, long npx) {
   }
 }
 
-// 96 -> 96 1x1, NHWC views with 16-byte aligned pixels (g / x stride and offset % 4 == 0)
-bool wgrad1p_ok(const WgradArgs& a) {
-  if (a.Cout != 96 || a.Cin != 96 || a.zc > 0) return false;
-  if ((a.g_stride | a.g_off | a.x_stride | a.x_off) & 3) return false;
-  return a.g_off + 96 <= a.g_stride && a.x_off + 96 <= a.x_stride &&
-         32L * a.g_stride * 4 < 0x7fffffffL && 32L * a.x_stride * 4 < 0x7fffffffL;
-}
-
-// k_wgrad1p over `splits` slab rows of [W (co, ci) | b] (a.slab, a.slab_stride >= 96*96 + 96);
-// up2: 4 x splits rows of [W (ci, co) | b], parity-major (a.KH x a.KW = the low-res input)
-hipError_t launch_wgrad1p(const WgradArgs& a, int splits, hipStream_t s, bool up2) {
-  if (!wgrad1p_ok(a) || splits < 1 || a.slab_stride < 96 * 96 + 96) return hipErrorInvalidValue;
+// k_wgrad1p over r.splits slab rows of [W (co, ci) | b] (a.slab, a.slab_stride = 96*96 + 96);
+// deconv: 4 x splits rows of [W (ci, co) | b], parity-major (a.KH x a.KW = the low-res input;
+// the flat grid's block -> (split, parity) map needs the route's whole groups of 8 splits)
+hipError_t launch_wgrad1p(const WgradArgs& a, const WgradRoute& r, hipStream_t s) {
+  if (r.kernel != WK_WGRAD1P) return hipErrorInvalidValue;
   const long npx = (long)a.N * a.KH * a.KW;
-  if (up2) {
-    // (the flat grid's block -> (split, parity) map needs whole groups of 32 blocks)
-    if (splits % 8) return hipErrorInvalidValue;
+  const int splits = r.splits;
+  if (r.par == 4) {
     prof_kernel("k_wgrad1p<true>");
     hipLaunchKernelGGL(k_wgrad1p<true>, dim3(4 * splits), dim3(256), 0, s, a, npx);
   } else if (a.head_gnb > 0) {
     // (hd_wc is read with 16-byte loads; a dy pixel holds head_gnb values)
-    if (a.head_gnb > 4 || !a.hd_dy || !a.hd_wc || a.g_stride != 96 || a.g_off ||
-        (reinterpret_cast<uintptr_t>(a.hd_wc) & 15) || a.hd_dy_stride < a.head_gnb ||
-        (a.hd_slab_c && a.head_gnb != 1))  // (the nin_c fold: one output only)
+    if (!a.hd_dy || !a.hd_wc || (reinterpret_cast<uintptr_t>(a.hd_wc) & 15) ||
+        a.hd_dy_stride < a.head_gnb || (a.hd_slab_c && a.head_gnb != 1))  // (the nin_c fold: one output only)
       return hipErrorInvalidValue;
     prof_kernel("k_wgrad1p<false,gnb>");
 #define DN_GNB(K) hipLaunchKernelGGL((k_wgrad1p<false, K>), dim3(splits), dim3(256), 0, s, a, npx)
@@ -1114,6 +1093,5 @@ hipError_t launch_wgrad1p(const WgradArgs& a, int splits, hipStream_t s, bool up
   }
   return hipGetLastError();
 }
-
 
 }  // namespace dn

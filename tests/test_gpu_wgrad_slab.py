@@ -93,7 +93,7 @@ def _wgrad(dz, x, x_stride, x6, prefix=None):
     gd.check(what=f"dwb ({label})")
     gx.check(what=f"x ({label})")
     gdz.check(what=f"dz ({label})")
-    # the launched split count: what the slab was sized for, capped by wgrad_splits_x6 at one
+    # the launched split count: what the slab was sized for, capped by the route (wgrad_route.cpp) at one
     # round of 512 workgroups over the input-channel blocks (32 per block at 96 outputs, else 48)
     cib = 32 if cout == 96 else 48
     return gd.data.reshape(-1).cpu().numpy(), label, min((nfl - 64) // n, 512 // -(-cin // cib))
