@@ -11,7 +11,7 @@ from .improved_unet import ImprovedUNet  # noqa: F401
 from .n2n import (AugmentNoise, generate_mask_pair, generate_subimages,  # noqa: F401
                   n2n_loss, n2n_subsample)
 from .resnet import RESNET  # noqa: F401
-from .optim import FlatAdam, lr_at_epoch  # noqa: F401
+from .optim import FlatAdam, GradGuard, lr_at_epoch  # noqa: F401
 from .trainer import N2NTrainer, StructureTrainer, SupervisedTrainer  # noqa: F401
 from .util import L1FFT, Structure_loss  # noqa: F401
 

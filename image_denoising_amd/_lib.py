@@ -29,6 +29,13 @@ class DnCfg(ctypes.Structure):
     _fields_ = [("in_nc", c_int), ("out_nc", c_int), ("n_feature", c_int)]
 
 
+class DnGuardStats(ctypes.Structure):  # include/denoise_hip.h dn_guard_stats
+    _fields_ = [("step", c_int64), ("applied", c_int64), ("skipped_loss", c_int64),
+                ("skipped_norm", c_int64), ("last_norm", c_double), ("last_coef", c_float),
+                ("apply", ctypes.c_int32), ("gscale", c_float), ("step_size", c_float),
+                ("bc2s", c_float), ("last_loss", c_float)]
+
+
 _F = c_void_p  # float*  (device)
 _U8 = c_void_p  # uint8_t* (device)
 
@@ -95,6 +102,12 @@ SIGNATURES = {
                               c_void_p, c_size_t, c_void_p]),
     "dn_adam_step": (c_int, [_F, _F, _F, _F, c_int64, c_float, c_float, c_float, c_float, c_int64,
                              c_float, c_void_p]),
+    "dn_guard_state_size": (c_size_t, []),
+    "dn_guard_state_init": (c_int, [c_void_p, c_int64, c_void_p]),
+    "dn_grad_norm": (c_int, [_F, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "dn_adam_step_guarded": (c_int, [_F, _F, _F, _F, c_int64, c_float, c_float, c_float, c_float,
+                                     c_float, _F, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "dn_guard_state_read": (c_int, [c_void_p, POINTER(DnGuardStats), c_void_p]),
     "dn_conv2d_pack_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dn_deconv2x2_pack_size": (c_size_t, [c_int, c_int, c_int]),
     "dn_conv2d_forward": (c_int, [_F, c_int, c_int, c_int, c_int, c_int, _F, _F, c_int, c_int,

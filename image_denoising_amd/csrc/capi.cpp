@@ -544,6 +544,54 @@ dn_status dn_adam_step(float* param, const float* grad, float* exp_avg, float* e
                     "dn_adam_step");
 }
 
+size_t dn_guard_state_size(void) { return guard_state_bytes(); }
+
+static bool guard_state_ok(const void* state) {
+  return state && (reinterpret_cast<uintptr_t>(state) & 15) == 0;
+}
+
+dn_status dn_guard_state_init(void* state, int64_t step, void* stream) {
+  if (!guard_state_ok(state)) return fail(DN_ERR_ARG, "guard state must be non-null and 16-byte aligned");
+  if (step < 0) return fail(DN_ERR_ARG, "step >= 0 required");
+  return hip_status(launch_guard_init(state, step, (hipStream_t)stream), "dn_guard_state_init");
+}
+
+dn_status dn_grad_norm(const float* grad, int64_t n, float grad_scale, void* state,
+                       double* norm_out, void* stream) {
+  if (n < 0) return fail(DN_ERR_ARG, "n < 0");
+  if (n == 0) return DN_OK;
+  if (!grad) return fail(DN_ERR_ARG, "null argument");
+  if (!guard_state_ok(state)) return fail(DN_ERR_ARG, "guard state must be non-null and 16-byte aligned");
+  const OpTimer timer((hipStream_t)stream, "grad_norm", 0);
+  return hip_status(launch_grad_norm(grad, n, grad_scale, state, norm_out, (hipStream_t)stream),
+                    "dn_grad_norm");
+}
+
+dn_status dn_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                               int64_t n, float lr, float beta1, float beta2, float eps,
+                               float grad_scale, const float* loss, float max_loss,
+                               float max_norm_skip, float clip, void* state, void* stream) {
+  if (n < 0) return fail(DN_ERR_ARG, "n < 0");
+  if (n == 0) return DN_OK;
+  if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(DN_ERR_ARG, "null argument");
+  if (!guard_state_ok(state)) return fail(DN_ERR_ARG, "guard state must be non-null and 16-byte aligned");
+  // the doubles torch forms from its Python floats, as dn_adam_step; the step-dependent scalars
+  // are formed from them on the device, where the step count lives
+  const double b1 = as_written(beta1), b2 = as_written(beta2);
+  const auto on = [](float x) { return x > 0.f ? x : 0.f; };  // <= 0 and NaN: the guard is off
+  const OpTimer timer((hipStream_t)stream, "adam_guarded", 0);
+  return hip_status(launch_adam_guarded(param, grad, exp_avg, exp_avg_sq, n, (float)(1.0 - b1),
+                                        beta2, (float)(1.0 - b2), eps, grad_scale, as_written(lr),
+                                        b1, b2, loss, on(max_loss), on(max_norm_skip), on(clip),
+                                        state, (hipStream_t)stream),
+                    "dn_adam_step_guarded");
+}
+
+dn_status dn_guard_state_read(const void* state, dn_guard_stats* out, void* stream) {
+  if (!guard_state_ok(state) || !out) return fail(DN_ERR_ARG, "null argument or unaligned guard state");
+  return hip_status(guard_state_read(state, out, (hipStream_t)stream), "dn_guard_state_read");
+}
+
 dn_status dn_accumulate(float* dst, const float* src, int64_t n, void* stream) {
   if (n < 0) return fail(DN_ERR_ARG, "n < 0");
   if (n == 0) return DN_OK;

@@ -421,6 +421,18 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
                        float b2, float w2, float step_size, float bc2s, float eps, float gscale,
                        hipStream_t s);
 
+// ---- guarded optimizer step (guard.hip): state = guard_state_bytes(), 16-byte aligned
+size_t guard_state_bytes();
+hipError_t launch_guard_init(void* state, int64_t step, hipStream_t s);
+hipError_t launch_grad_norm(const float* g, int64_t n, float gscale, void* state, double* norm_out,
+                            hipStream_t s);
+hipError_t launch_adam_guarded(float* p, const float* g, float* m, float* v, int64_t n, float w1,
+                               float b2f, float w2, float eps, float gscale, double lr, double b1,
+                               double b2, const float* loss, float max_loss, float max_norm_skip,
+                               float clip, void* state, hipStream_t s);
+// out: a host dn_guard_stats; synchronises s
+hipError_t guard_state_read(const void* state, void* out, hipStream_t s);
+
 // ---- mixed-precision (bf16 MFMA) 3x3 forward (conv_bf16.hip) ----
 long bf16_pack_elems(int K, int nout, int ksize = 3);
 long bf16_stage_elems(int nout, int ksize);  // bf16 per weight stage of the image (-1: no tile)

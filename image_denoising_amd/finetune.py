@@ -229,7 +229,7 @@ class _AdapterStepBase(_FlatStepBase):
     the adapter's flat buffer, the step's buffers and the workspace-reusing frozen-base call."""
 
     def __init__(self, model, lr: float, lambda_grad: float, distributed: bool | None,
-                 lambda_iqsl: float, iqsl: dict | None):
+                 lambda_iqsl: float, iqsl: dict | None, guard=None):
         self.model = model
         self.lambda_grad = lambda_grad
         self.lambda_iqsl = float(lambda_iqsl)
@@ -246,7 +246,8 @@ class _AdapterStepBase(_FlatStepBase):
         # frozen base when it is one of ours (loaded per rank from one checkpoint)
         base = model.base
         self._init_step(model.adapter.flat_params, lr, distributed,
-                        frozen=base.flat_params.data if isinstance(base, HipNet) else None)
+                        frozen=base.flat_params.data if isinstance(base, HipNet) else None,
+                        guard=guard)
 
     def _buffers(self, shape, device):
         key = (tuple(shape), device)
@@ -277,14 +278,15 @@ class FinetuneTrainer(_AdapterStepBase):
     lambda_iqsl > 0 makes it the finetune_iqsl.py:469-494 step: `iqsl` = dict(t1, t2[, tau,
     margin, ce_factor]) (the thresholds from `estimate_intensity_thresholds`), and the step returns
     loss4 = [loss_l1, loss_grad, loss_iqsl, loss].  Each rank's loss is the mean over its own
-    batch, as an nn.DataParallel replica computes it."""
+    batch, as an nn.DataParallel replica computes it.  guard: optim.GradGuard around the update,
+    tested against the total (the last entry)."""
 
     def __init__(self, model: DenoiserWithAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
                  distributed: bool | None = None, lambda_iqsl: float = 0.0,
-                 iqsl: dict | None = None):
+                 iqsl: dict | None = None, guard=None):
         if not isinstance(model, DenoiserWithAdapter):
             raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
-        super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl)
+        super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl, guard)
 
     def train_step(self, clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
         clean, noisy = clean.contiguous(), noisy.contiguous()
@@ -296,5 +298,5 @@ class FinetuneTrainer(_AdapterStepBase):
         ad._run_forward(noisy, b["base"], b["pred"])
         loss3, dpred = self._loss(b["pred"], clean)
         ad._run_backward(noisy, b["base"], dpred, self.grad)
-        self._update()
+        self._update(loss=loss3[-1] if self.guard is not None else None)
         return loss3

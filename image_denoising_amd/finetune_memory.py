@@ -23,14 +23,15 @@ from .memory import DenoiserWithMemoryAdapter
 
 class MemoryFinetuneTrainer(_AdapterStepBase):
     """Returns loss4 = [loss_l1, loss_grad, loss_iqsl, loss] when lambda_iqsl > 0 (`iqsl` =
-    dict(t1, t2[, tau, margin, ce_factor])), else loss3 = [loss_l1, loss_grad, loss]."""
+    dict(t1, t2[, tau, margin, ce_factor])), else loss3 = [loss_l1, loss_grad, loss].  guard:
+    optim.GradGuard around the update, tested against the total (the last entry)."""
 
     def __init__(self, model: DenoiserWithMemoryAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
                  distributed: bool | None = None, lambda_iqsl: float = 0.0,
-                 iqsl: dict | None = None):
+                 iqsl: dict | None = None, guard=None):
         if not isinstance(model, DenoiserWithMemoryAdapter):
             raise TypeError("MemoryFinetuneTrainer drives a DenoiserWithMemoryAdapter")
-        super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl)
+        super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl, guard)
 
     def train_step(self, clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
         clean, noisy = clean.contiguous(), noisy.contiguous()
@@ -43,5 +44,5 @@ class MemoryFinetuneTrainer(_AdapterStepBase):
         feat = ad._run_forward(noisy, b["base"], mem, b["pred"])
         loss, dpred = self._loss(b["pred"], clean)
         ad._run_backward(noisy, b["base"], feat, dpred, self.grad)
-        self._update()
+        self._update(loss=loss[-1] if self.guard is not None else None)
         return loss

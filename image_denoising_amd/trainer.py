@@ -25,7 +25,7 @@ from . import _lib
 from . import dist as dp
 from .arch_unet import UNet
 from .n2n import AugmentNoise, _partials_for, n2n_loss, n2n_subsample
-from .optim import FlatAdam, lr_at_epoch
+from .optim import FlatAdam, GradGuard, lr_at_epoch
 from .util import L1FFT_RULE, l1fft_loss_into, l1fft_supported, structure_loss_into
 
 
@@ -35,36 +35,61 @@ class _FlatStepBase:
     step."""
 
     def _init_step(self, flat: torch.Tensor, lr: float, distributed: bool | None,
-                   frozen: torch.Tensor | None = None) -> None:
-        """`flat`: the trained buffer; `frozen`: parameters that are only made identical"""
+                   frozen: torch.Tensor | None = None, guard: GradGuard | None = None) -> None:
+        """`flat`: the trained buffer; `frozen`: parameters that are only made identical;
+        `guard`: train_opt.py:128-157's guards around the update (optim.GradGuard)"""
         self.distributed = dp.require_group(distributed)
         if self.distributed:  # identical replicas: broadcast rank 0's initial weights
             if frozen is not None:
                 dp.broadcast_params(frozen)
             dp.broadcast_params(flat)
-        self.opt = FlatAdam(flat, lr=lr)
+        self.guard = guard
+        self.opt = FlatAdam(flat, lr=lr, guard=guard)
         self.grad = torch.zeros_like(flat)
         self._bufs = {}
 
-    def _adam(self, scale: float, epoch: int | None = None) -> None:
-        """Adam(W, scale * grad), at the schedule's lr of `epoch` when one is given"""
+    def _guard_loss(self, loss: torch.Tensor | None) -> torch.Tensor | None:
+        """What the guarded step tests: this step's total loss (a device view), averaged over the
+        ranks so that every rank takes the same decision (one 4-byte collective; a NaN on one rank
+        skips the step on all).  None without a guard."""
+        if self.guard is None or loss is None:
+            return None
+        if self.distributed:
+            loss = dp.allreduce_mean_(loss.detach().clone().reshape(1))
+        return loss
+
+    def _adam(self, scale: float, epoch: int | None = None,
+              loss: torch.Tensor | None = None) -> None:
+        """Adam(W, scale * grad), at the schedule's lr of `epoch` when one is given; with a guard
+        the update is withheld or clipped on the device (`loss`: what _guard_loss returned)"""
         if epoch is not None:
             self.opt.lr = lr_at_epoch(epoch, self.base_lr, self.n_epoch, self.gamma)
-        self.opt.step(self.grad, grad_scale=scale)
+        if self.guard is None:
+            self.opt.step(self.grad, grad_scale=scale)
+        else:
+            self.opt.step(self.grad, grad_scale=scale, loss=loss)
 
-    def _update(self, epoch: int | None = None) -> None:
-        """one RCCL all-reduce(sum) of the flat gradient (1/world folded into Adam), then Adam"""
-        self._adam(dp.allreduce_grads(self.grad) if self.distributed else 1.0, epoch)
+    def _update(self, epoch: int | None = None, loss: torch.Tensor | None = None) -> None:
+        """one RCCL all-reduce(sum) of the flat gradient (1/world folded into Adam), then Adam;
+        `loss`: the step's total loss as a device view, for the guard"""
+        loss = self._guard_loss(loss)
+        self._adam(dp.allreduce_grads(self.grad) if self.distributed else 1.0, epoch, loss)
+
+    def guard_stats(self) -> dict:
+        """the guarded optimizer's counters and last decision (FlatAdam.guard_stats; syncs)"""
+        return self.opt.guard_stats()
 
 
 class N2NTrainer(_FlatStepBase):
     def __init__(self, net: UNet, lr: float = 3e-4, n_epoch: int = 100,
                  increase_ratio: float = 2.0, gamma: float = 0.5, noise_std: float = 25.0 / 255.0,
-                 seed: int = 0, distributed: bool | None = None, noise_style: str | None = None):
+                 seed: int = 0, distributed: bool | None = None, noise_style: str | None = None,
+                 guard: GradGuard | None = None):
         """noise_style: a train.py --noisetype ('gauss25', 'gauss5_50', 'poisson30',
         'poisson5_50'); None = Gaussian of std noise_std.  Range styles draw one value per image
         of the GLOBAL batch (seeded by the step), so a rank's shard sees the same values as the
-        single-process run."""
+        single-process run.  guard: optim.GradGuard, tested against loss3[2] (None: the plain
+        update)."""
         self.net = net
         self.base_lr = lr
         self.n_epoch = n_epoch
@@ -73,7 +98,7 @@ class N2NTrainer(_FlatStepBase):
         self.noise_std = noise_std
         self.noise = AugmentNoise(noise_style) if noise_style else None
         self.seed = seed
-        self._init_step(net.flat_params, lr, distributed)
+        self._init_step(net.flat_params, lr, distributed, guard=guard)
         self.world, self.rank = dp.world_and_rank() if self.distributed else (1, 0)
         self.global_step = 0
         # the overlapped all-reduce needs the split backward (arch_unet.UNet); other nets
@@ -172,13 +197,14 @@ class N2NTrainer(_FlatStepBase):
         # the decoder + head one overlapping the encoder's backward (DN_AR_OVERLAP=0: one
         # all-reduce after the whole backward)
         if self.distributed and self._overlap:
+            guard_loss = self._guard_loss(loss3[2] if self.guard is not None else None)
             self._adam(dp.allreduce_grads_split(
                 self.grad, self._tail_begin,
                 lambda ev: self._backward(dout, b["ws_grad"], N, H // 2, W // 2, ev),
-                self._comm_stream(clean.device)), epoch)
+                self._comm_stream(clean.device)), epoch, guard_loss)
         else:
             self.net._run_backward(dout, self.grad, b["ws_grad"], N, H // 2, W // 2)
-            self._update(epoch)
+            self._update(epoch, loss3[2] if self.guard is not None else None)
         self.global_step += 1
         return loss3
 
@@ -203,11 +229,12 @@ class StructureTrainer(_FlatStepBase):
     """
 
     def __init__(self, net: UNet, lr: float = 3e-4, n_epoch: int = 100, gamma: float = 0.5,
-                 alpha_beta_gamma=(1.0, 0.5, 0.5), distributed: bool | None = None):
+                 alpha_beta_gamma=(1.0, 0.5, 0.5), distributed: bool | None = None,
+                 guard: GradGuard | None = None):
         self.net = net
         self.base_lr, self.n_epoch, self.gamma = lr, n_epoch, gamma
         self.weights = alpha_beta_gamma
-        self._init_step(net.flat_params, lr, distributed)
+        self._init_step(net.flat_params, lr, distributed, guard=guard)
 
     def _buffers(self, N, C, H, W, device):
         key = (N, C, H, W, device)
@@ -236,13 +263,14 @@ class StructureTrainer(_FlatStepBase):
         pred, pred2 = b["pred"][:N], b["pred"][N:]
         structure_loss_into(pred, pred2, clean, a, be, g, b["dpred"][:N], b["dpred"][N:], b["loss5"])
         self.net._run_backward(b["dpred"], self.grad, b["ws"], 2 * N, H, W)
-        self._update(epoch)
+        self._update(epoch, b["loss5"][4] if self.guard is not None else None)
         return b["loss5"].clone()
 
 
 class SupervisedTrainer(_FlatStepBase):
     """The plain supervised step `criterion(network(noisy), clean)` (train.py:362 with the
-    criterion of train.py:318-321; train_opt.py:122-157 without its guards), fused:
+    criterion of train.py:318-321; with `guard=GradGuard()` train_opt.py:122-157, guards
+    included), fused:
 
         pred = net(noisy)                   [saved]   _run_forward
         loss3, dpred = criterion(pred, clean)         dn_l1fft_loss ('l1fft', util.py:5-38)
@@ -250,6 +278,15 @@ class SupervisedTrainer(_FlatStepBase):
         dW = backward(dpred)                          _run_backward
         [data parallel: one RCCL all-reduce(sum) of dW]
         Adam(W, dW / world)                           dn_adam_step
+        [guard: norm, decision, Adam                  dn_adam_step_guarded (train_opt.py:128-157)]
+
+    The guards (optim.GradGuard: grad_clip 1.0, max_loss_skip 5.0, max_grad_norm 20.0) skip the
+    update when loss3[2] is non-finite or above max_loss_skip, or when the gradient norm is
+    non-finite or above 10 * max_grad_norm, and clip the gradient to norm grad_clip otherwise, all
+    decided on the device: the step still reads nothing back.  A non-finite pixel in the prediction
+    or the target makes the loss non-finite, which is the reference's first test (:129).  The
+    backward of a skipped batch still runs; only the update is withheld.  guard_stats() counts the
+    applied and skipped steps.
 
     One forward and one backward of N images (StructureTrainer with weights (1, 0, 0) gives the
     same loss from a 2N batch whose second half gets zero gradient).  net: UNet, RESNET or
@@ -261,13 +298,13 @@ class SupervisedTrainer(_FlatStepBase):
 
     def __init__(self, net, criterion: str = "l1fft", alpha: float = 1.0, beta: float = 1.0,
                  lr: float = 3e-4, n_epoch: int = 100, gamma: float = 0.5,
-                 distributed: bool | None = None):
+                 distributed: bool | None = None, guard: GradGuard | None = None):
         if criterion not in ("l1", "l1fft"):
             raise ValueError("criterion must be 'l1' or 'l1fft'")
         self.net = net
         self.criterion, self.alpha, self.beta = criterion, alpha, beta
         self.base_lr, self.n_epoch, self.gamma = lr, n_epoch, gamma
-        self._init_step(net.flat_params, lr, distributed)
+        self._init_step(net.flat_params, lr, distributed, guard=guard)
 
     def _buffers(self, N, H, W, device):
         key = (N, H, W, device)
@@ -297,5 +334,5 @@ class SupervisedTrainer(_FlatStepBase):
                       _partials_for(clean.device).data_ptr(), _lib.stream_of(clean))
             b["loss3"][1].zero_()  # the unweighted gradient-L1 the kernel also reports
         self.net._run_backward(b["dpred"], self.grad, b["ws"], N, H, W)
-        self._update(epoch)
+        self._update(epoch, b["loss3"][2] if self.guard is not None else None)
         return b["loss3"].clone()

@@ -270,6 +270,50 @@ dn_status dn_adam_step(float* param, const float* grad, float* exp_avg, float* e
                        float lr, float beta1, float beta2, float eps, int64_t step,
                        float grad_scale, void* stream);
 
+/* ---- guarded optimiser step: train_opt.py:128-157 with no host synchronisation ------- */
+/* What the guard state holds for the host (dn_guard_state_read).  step counts the applied
+   steps only: it is Adam's bias-correction count, kept on the device because the host does not
+   know whether a step was skipped.  The last_* fields and apply describe the latest decision;
+   gscale = last_coef * grad_scale, step_size and bc2s are the scalars the Adam kernel read
+   (0, 0, 1 after a skip). */
+typedef struct dn_guard_stats {
+  int64_t step;
+  int64_t applied;
+  int64_t skipped_loss;
+  int64_t skipped_norm;
+  double last_norm;
+  float last_coef;
+  int32_t apply;
+  float gscale;
+  float step_size;
+  float bc2s;
+  float last_loss;
+} dn_guard_stats;
+
+/* Bytes of the caller-owned, 16-byte aligned device state: the norm's fp64 block partials and a
+   dn_guard_stats.  dn_guard_state_init zeroes the counters and sets the step count (0 for a fresh
+   optimiser, a checkpoint's value on resume). */
+size_t dn_guard_state_size(void);
+dn_status dn_guard_state_init(void* state, int64_t step, void* stream);
+/* The L2 norm of grad_scale * grad (the product formed in fp32 as dn_adam_step forms it, squares
+   and sums in fp64, fixed order: the same bits run to run) into the state's last_norm and, when
+   norm_out (device) is not NULL, there.  grad is only read. */
+dn_status dn_grad_norm(const float* grad, int64_t n, float grad_scale, void* state,
+                       double* norm_out, void* stream);
+/* dn_adam_step behind train_opt.py's guards, decided on the device in the reference's order:
+   skip when loss (device, may be NULL: no loss test) is non-finite or > max_loss; else skip when
+   the norm of grad_scale * grad is non-finite or > max_norm_skip; else scale the gradient by
+   min(1, clip / (norm + 1e-6)) (clip_grad_norm_) inside the Adam pass, count the step and update.
+   A value <= 0 or NaN for max_loss, max_norm_skip or clip turns that guard off; a non-finite norm
+   skips unless both norm guards are off.  A skipped step leaves param, exp_avg, exp_avg_sq and
+   the step count unchanged bit for bit; grad is never written.  Three launches on stream. */
+dn_status dn_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                               int64_t n, float lr, float beta1, float beta2, float eps,
+                               float grad_scale, const float* loss, float max_loss,
+                               float max_norm_skip, float clip, void* state, void* stream);
+/* Copies the state's dn_guard_stats to out (host) and synchronises stream: the only read-back. */
+dn_status dn_guard_state_read(const void* state, dn_guard_stats* out, void* stream);
+
 /* dst += src over n floats (sums the parameter gradients of several backward passes, e.g.
    the two network evaluations of the Structure_loss step, train.py:361-367) */
 dn_status dn_accumulate(float* dst, const float* src, int64_t n, void* stream);
