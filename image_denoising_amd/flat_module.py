@@ -121,12 +121,19 @@ class HipNet(FlatParamModule):
         self.in_nc, self.out_nc, self.n_feature = in_nc, out_nc, n_feature
         self._cfg = _lib.cfg(in_nc, out_nc, n_feature)
         self._ws_cache = {}
-
-    def _bind_net(self, flat: torch.Tensor, entries) -> None:
+        # the library's own check of the configuration, before any parameter is drawn: channel
+        # counts or a width no kernel is built for are the caller's ValueError (DN_ERR_ARG)
         n = ctypes.c_size_t()
         what = f"dn_{self._family}_param_count"
-        _lib.check(getattr(_lib.lib(), what)(ctypes.byref(self._cfg), ctypes.byref(n)), what)
-        assert flat.numel() == n.value, (flat.numel(), n.value)
+        status = getattr(_lib.lib(), what)(ctypes.byref(self._cfg), ctypes.byref(n))
+        if status == -1:
+            raise ValueError(f"{self._display}(in_nc={in_nc}, out_nc={out_nc}, "
+                             f"n_feature={n_feature}): {_lib.last_error()}")
+        _lib.check(status, what)
+        self._param_count = n.value
+
+    def _bind_net(self, flat: torch.Tensor, entries) -> None:
+        assert flat.numel() == self._param_count, (flat.numel(), self._param_count)
         self._bind_flat(flat, entries)
 
     def _drop_scratch(self) -> None:

@@ -111,6 +111,24 @@ def new_trace():
     return _Trace()
 
 
+def pool_gap(flat: torch.Tensor, x: torch.Tensor, in_nc: int, out_nc: int) -> float:
+    """smallest gap between the two largest values of any 2x2 max-pool window of the float64
+    forward.  MaxPool routes the whole gradient to the argmax: where two candidates lie within
+    fp32 rounding of each other, two fp32 implementations may route differently and every
+    gradient upstream moves by O(1e-3); a comparison of gradients is well posed only on inputs
+    whose gap is well above that rounding."""
+    tr = new_trace()
+    with torch.no_grad():
+        forward(flat.double(), x.double(), in_nc, out_nc, trace=tr)
+    gaps = []
+    for i in range(4):
+        s = tr.res[f"downs.{i}.3"]["out"]
+        n, c, h, w = s.shape
+        top = s.unfold(2, 2, 2).unfold(3, 2, 2).reshape(n, c, h // 2, w // 2, 4).topk(2, -1).values
+        gaps.append(float((top[..., 0] - top[..., 1]).min()))
+    return min(gaps)
+
+
 def forward(flat: torch.Tensor, x: torch.Tensor, in_nc: int, out_nc: int, nf: int = 48,
             trace: list | None = None):
     """arch_unet.py:518-531.  `trace` (optional list) receives (name, NCHW tensor) of the

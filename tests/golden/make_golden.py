@@ -1,6 +1,6 @@
 """Generates tests/golden/*.npz from the REFERENCE implementation (build container only).
 
-Run:  python tests/golden/make_golden.py [/root/reference]
+Run:  python tests/golden/make_golden.py [/root/reference] [--only unet|iunet|adapter|unet_pairs|iunet_pairs]
 
 What it executes from the reference (read from its source tree, nothing is copied into this
 repo):
@@ -197,6 +197,76 @@ def unet_main():
     print("UNet fixtures written to", OUT)
 
 
+# (in_nc, out_nc) the fixtures above do not reach: in_nc 2 and 4, out_nc above 4, in_nc != out_nc
+UNET_PAIRS = ((2, 2), (4, 16), (3, 1))
+IUNET_PAIRS = ((2, 2), (1, 4), (3, 2))
+NSAMPLE_PAIRS = 8192
+
+
+def unet_pairs_main():
+    """arch_unet.UNet at UNET_PAIRS (unet_c<in>_<out>.npz), 1 x in_nc x 32 x 32, the seed-0
+    init: output, dL/dx, a gradient sample and the per-tensor gradient norms of mean(y^2)."""
+    sys.path.insert(0, REF)
+    import arch_unet  # noqa: E402
+
+    for C, OC in UNET_PAIRS:
+        torch.manual_seed(0)
+        net = arch_unet.UNet(in_nc=C, out_nc=OC, n_feature=48)
+        flat = flat_params(net)
+        x = torch.rand(1, C, 32, 32, generator=torch.Generator().manual_seed(10 * C + OC))
+        x.requires_grad_(True)
+        y = net(x)
+        loss = (y ** 2).mean()
+        loss.backward()
+        grad = torch.cat([p.grad.reshape(-1) for p in net.parameters()]).numpy()
+        idx = np.sort(np.random.default_rng(0).choice(grad.size, NSAMPLE_PAIRS, replace=False))
+        np.savez_compressed(
+            os.path.join(OUT, f"unet_c{C}_{OC}.npz"), x=x.detach().numpy(), y=y.detach().numpy(),
+            loss=np.float32(loss.item()), dx=x.grad.numpy(), params_sha=np.array(sha(flat)),
+            params_count=np.int64(flat.size), grad_idx=idx, grad_sample=grad[idx],
+            grad_norms=np.array([np.linalg.norm(p.grad.numpy()) for p in net.parameters()]))
+    print("UNet channel-count fixtures written to", OUT)
+
+
+def iunet_pairs_main():
+    """arch_unet.ImprovedUNet at IUNET_PAIRS (iunet_c<in>_<out>.npz), 1 x in_nc x 32 x 32, the
+    seed-0 init.  The input's seed is the first whose 2x2 pool windows all have a clear winner
+    in the float64 restatement (oracle.iunet_ref.pool_gap >= 1e-5), so fp32 implementations
+    route the pools' gradients alike."""
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    import arch_unet  # noqa: E402
+    from oracle import iunet_ref  # noqa: E402
+
+    for C, OC in IUNET_PAIRS:
+        torch.manual_seed(0)
+        net = arch_unet.ImprovedUNet(in_nc=C, out_nc=OC, n_feature=48)
+        flat = flat_params(net)
+        for seed in range(1, 200):
+            g = torch.Generator().manual_seed(seed)
+            x = torch.rand(1, C, 32, 32, generator=g)
+            t = torch.rand(1, OC, 32, 32, generator=g)
+            gap = iunet_ref.pool_gap(torch.from_numpy(flat), x, C, OC)
+            if gap >= 1e-5:
+                break
+        else:
+            raise SystemExit(f"no input seed with a pool gap >= 1e-5 for {(C, OC)}")
+        y = net(x)
+        loss = ((y - t) ** 2).mean()
+        loss.backward()
+        grad = torch.cat([p.grad.reshape(-1) for p in net.parameters()]).numpy()
+        idx = np.sort(np.random.default_rng(0).choice(grad.size, NSAMPLE_PAIRS, replace=False))
+        np.savez_compressed(
+            os.path.join(OUT, f"iunet_c{C}_{OC}.npz"), x=x.numpy(), t=t.numpy(),
+            y=y.detach().numpy(), loss=np.float32(loss.item()), params_sha=np.array(sha(flat)),
+            params_count=np.int64(flat.size), grad_idx=idx, grad_sample=grad[idx],
+            grad_norms=np.array([np.linalg.norm(p.grad.numpy()) for p in net.parameters()]),
+            keys=np.array(list(net.state_dict().keys())), x_seed=np.int64(seed),
+            pool_gap=np.float64(gap))
+        print(f"iunet_c{C}_{OC}.npz: input seed {seed}, pool gap {gap:.3g}")
+    print("ImprovedUNet channel-count fixtures written to", OUT)
+
+
 def adapter_main():
     """adapter.py OutputAdapter / DenoiserWithAdapter (imported) and finetune.py's gradient /
     gradient_loss (AST-extracted: finetune.py imports torchvision, absent here)."""
@@ -281,8 +351,12 @@ def iunet_main():
 
 if __name__ == "__main__":
     if "--only" in sys.argv:
-        {"adapter": adapter_main, "iunet": iunet_main, "unet": unet_main}[sys.argv[sys.argv.index("--only") + 1]]()
+        {"adapter": adapter_main, "iunet": iunet_main, "unet": unet_main,
+         "unet_pairs": unet_pairs_main,
+         "iunet_pairs": iunet_pairs_main}[sys.argv[sys.argv.index("--only") + 1]]()
     else:
         main()
         adapter_main()
         iunet_main()
+        unet_pairs_main()
+        iunet_pairs_main()

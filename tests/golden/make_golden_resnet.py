@@ -1,7 +1,7 @@
-"""Generates tests/golden/resnet_c1.npz and resnet_c3.npz from the REFERENCE RESNET (build
+"""Generates tests/golden/resnet_c1.npz .. resnet_c4.npz from the REFERENCE RESNET (build
 container only; the GPU box never needs the reference).
 
-Run:  python tests/golden/make_golden_resnet.py /path/to/reference
+Run:  python tests/golden/make_golden_resnet.py /path/to/reference [fixture names]
 
 It imports the reference's arch_unet as a module (nothing is copied into this repository) and
 records data only: inputs, outputs, the seed-0 initialisation's fingerprint and gradients.
@@ -69,14 +69,24 @@ def one(arch_unet, C, shape, seed, name):
     print(name, "max|y-x| =", res, "loss =", loss.item())
 
 
+FIXTURES = {
+    "resnet_c1.npz": (1, (2, 1, 24, 40), 11),
+    "resnet_c3.npz": (3, (1, 3, 13, 22), 12),
+    # the two channel counts between and above: enc_conv0 / dec_conv1a's K = 98 and 100
+    "resnet_c2.npz": (2, (1, 2, 32, 32), 13),
+    "resnet_c4.npz": (4, (1, 4, 32, 32), 14),
+}
+
+
 def main():
-    if len(sys.argv) != 2:
+    if len(sys.argv) < 2:
         raise SystemExit(__doc__)
     sys.path.insert(0, sys.argv[1])
     import arch_unet
 
-    one(arch_unet, 1, (2, 1, 24, 40), 11, "resnet_c1.npz")
-    one(arch_unet, 3, (1, 3, 13, 22), 12, "resnet_c3.npz")
+    for name in sys.argv[2:] or FIXTURES:  # (named fixtures only, or all of them)
+        C, shape, seed = FIXTURES[name]
+        one(arch_unet, C, shape, seed, name)
 
 
 if __name__ == "__main__":

@@ -26,6 +26,9 @@ def _make(name):
     make, shape, n_in = {
         "UNet": (lambda: UNet(1, 1, 48), (1, 1, 32, 32), 1),
         "ImprovedUNet": (lambda: ImprovedUNet(1, 1, 48), (1, 1, 16, 16), 1),
+        # in_nc != out_nc: the output and its gradient have out_nc channels, dL/dx has in_nc
+        "UNet(2,5)": (lambda: UNet(2, 5, 48), (1, 2, 32, 32), 1),
+        "ImprovedUNet(2,4)": (lambda: ImprovedUNet(2, 4, 48), (1, 2, 16, 16), 1),
         "RESNET": (lambda: RESNET(1, 1, 48), (1, 1, 9, 17), 1),  # ragged: test_gpu_resnet's size
         "OutputAdapter": (lambda: OutputAdapter(1, 16), (1, 1, 8, 8), 2),
         "HyperGatedResidualAdapter_FFT": (lambda: HyperGatedResidualAdapter_FFT(1, 16),
@@ -38,7 +41,8 @@ def _make(name):
         with torch.no_grad():
             m.flat_params.copy_(0.2 * torch.randn(m.flat_params.shape, generator=g))
     inputs = [torch.rand(shape, generator=g).to(DEV) for _ in range(n_in)]
-    dy = torch.randn(shape, generator=g).to(DEV)
+    out_shape = (shape[0], m.out_nc) + shape[2:] if isinstance(m, HipNet) else shape
+    dy = torch.randn(out_shape, generator=g).to(DEV)
     return m.to(DEV), inputs, dy
 
 
@@ -71,7 +75,8 @@ def _autograd(m, inputs, dy):
     return [p.grad for p in m._params()]
 
 
-NAMES = ["UNet", "RESNET", "OutputAdapter", "HyperGatedResidualAdapter_FFT", "ImprovedUNet"]
+NAMES = ["UNet", "RESNET", "OutputAdapter", "HyperGatedResidualAdapter_FFT", "ImprovedUNet",
+         "UNet(2,5)", "ImprovedUNet(2,4)"]
 
 
 @pytest.fixture(scope="module", params=NAMES)
@@ -119,7 +124,7 @@ def test_input_gradient(case):
     call's with a dx buffer; ImprovedUNet and the adapters compute no input gradient and say so"""
     name, m, inputs, dy, _ = case
     x = inputs[0].clone().requires_grad_(True)
-    if name not in ("UNet", "RESNET"):
+    if name not in ("UNet", "RESNET", "UNet(2,5)"):
         with pytest.raises(NotImplementedError):
             m(x, *inputs[1:])
         return

@@ -31,11 +31,12 @@ def _gpu():
         pytest.skip("no GPU")
 
 
-def _net(C, prec="fp32"):
+def _net(C, prec="fp32", out_nc=None):
     from image_denoising_amd.improved_unet import ImprovedUNet
 
     torch.manual_seed(0)
-    return ImprovedUNet(in_nc=C, out_nc=C, n_feature=48).set_precision(prec)
+    return ImprovedUNet(in_nc=C, out_nc=C if out_nc is None else out_nc,
+                        n_feature=48).set_precision(prec)
 
 
 def _trace_mismatches(net, x, ws, flat_cpu, C):
@@ -48,7 +49,7 @@ def _trace_mismatches(net, x, ws, flat_cpu, C):
     _lib.call("dn_iunet_debug_buffers", ctypes.byref(net._cfg), N, H, W, 1, desc, 64,
               ctypes.byref(n))
     tr = []
-    iunet_ref.forward(flat_cpu, x.cpu(), C, C, trace=tr)
+    iunet_ref.forward(flat_cpu, x.cpu(), C, net.out_nc, trace=tr)
     fws = ws.view(torch.float32)
     out = []
     for i, (name, ref) in enumerate(tr):
@@ -63,15 +64,17 @@ def _trace_mismatches(net, x, ws, flat_cpu, C):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("C,name", [(1, "iunet_c1.npz"), (3, "iunet_c3.npz")])
+@pytest.mark.parametrize("C,name", [(1, "iunet_c1.npz"), (3, "iunet_c3.npz"), (2, "iunet_c2_2.npz"),
+                                    (1, "iunet_c1_4.npz"), (3, "iunet_c3_2.npz")])
 def test_forward_backward_vs_reference_fixture(golden, C, name, prec):
     g = golden(name)
-    net = _net(C, prec).to(DEV)
+    OC = g["t"].shape[1]  # (iunet_c<in_nc>_<out_nc>.npz: out_nc != in_nc)
+    net = _net(C, prec, OC).to(DEV)
     x = torch.from_numpy(g["x"]).to(DEV)
     t = torch.from_numpy(g["t"]).to(DEV)
     N, _, H, W = x.shape
     ws = net._workspace(N, H, W, with_backward=True, fresh=True)
-    y = torch.empty_like(x)
+    y = torch.empty_like(t)
     net._run_forward(x, y, ws)
     err = rel_err(y.cpu().numpy(), g["y"])
     assert err < FP32_TOL, (err, _trace_mismatches(net, x, ws, net.flat_params.cpu(), C))
@@ -89,7 +92,7 @@ def test_forward_backward_vs_reference_fixture(golden, C, name, prec):
     gr = grad.cpu().numpy()
     assert rel_err(gr[g["grad_idx"]], g["grad_sample"]) < GRAD_TOL
     norms, off = [], 0
-    for _, shape in iunet_ref.layer_table(C, C):
+    for _, shape in iunet_ref.layer_table(C, OC):
         k = int(np.prod(shape))
         norms.append(np.linalg.norm(gr[off:off + k]))
         off += k
@@ -99,24 +102,15 @@ def test_forward_backward_vs_reference_fixture(golden, C, name, prec):
     assert not bad, bad[:5]
 
 
-def _pool_gap(x, C):
+def _pool_gap(x, C, out_nc=None):
     """smallest gap between the two largest values of any 2x2 max-pool window of the fp64
-    oracle.  MaxPool routes the whole gradient to the argmax: where two candidates lie within
-    fp32 rounding of each other, any two fp32 implementations (torch CPU included) may route
-    differently and every gradient upstream moves by O(1e-3).  The parity inputs below are
-    chosen with gaps >= 1e-5 so the comparison is well-posed; ties themselves are exercised
-    bit-exactly by the maxpool tests."""
-    torch.manual_seed(0)
-    tr = iunet_ref.new_trace()
-    with torch.no_grad():
-        iunet_ref.forward(_net(C).flat_params.double(), x.double(), C, C, trace=tr)
-    gaps = []
-    for i in range(4):
-        s = tr.res[f"downs.{i}.3"]["out"]
-        n, c, h, w = s.shape
-        top = s.unfold(2, 2, 2).unfold(3, 2, 2).reshape(n, c, h // 2, w // 2, 4).topk(2, -1).values
-        gaps.append(float((top[..., 0] - top[..., 1]).min()))
-    return min(gaps)
+    oracle (iunet_ref.pool_gap).  MaxPool routes the whole gradient to the argmax: where two
+    candidates lie within fp32 rounding of each other, any two fp32 implementations (torch CPU
+    included) may route differently and every gradient upstream moves by O(1e-3).  The parity
+    inputs below are chosen with gaps >= 1e-5 so the comparison is well-posed; ties themselves
+    are exercised bit-exactly by the maxpool tests."""
+    OC = C if out_nc is None else out_nc
+    return iunet_ref.pool_gap(_net(C, out_nc=OC).flat_params, x, C, OC)
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -237,7 +231,7 @@ def _device_leaky_masks(net, ws, x, C, tr=None):
     if tr is None:  # (name, tensor) of every traced activation: only names and shapes are used
         tr = []
         with torch.no_grad():
-            iunet_ref.forward(net.flat_params.cpu().double(), x.double(), C, C, trace=tr)
+            iunet_ref.forward(net.flat_params.cpu().double(), x.double(), C, net.out_nc, trace=tr)
     fws = ws.view(torch.float32)
     dev = {}
     for i, (name, ref) in enumerate(tr):
@@ -320,6 +314,67 @@ def test_x6_grads_as_accurate_as_fp32_vs_fp64(golden, C, monkeypatch):
     print(f"\nC={C} y: fp32 {e32:.2e} x6 {e6:.2e}; grad max: fp32 {p32.max():.2e} x6 "
           f"{p6.max():.2e}; median: fp32 {np.median(p32):.2e} x6 {np.median(p6):.2e}")
     assert e6 < FP32_TOL and e6 < 4 * e32 + 1e-7, (e6, e32)
+    assert p6.max() < 4 * p32.max() + 1e-7, (p6.max(), p32.max())
+    assert np.median(p6) < 4 * np.median(p32) + 1e-7, (np.median(p6), np.median(p32))
+
+
+# (in_nc, out_nc), N x H x W, input seed.  The channel counts pick kernels: k_conv3_thin with 2 and
+# 4 outputs, the final conv's K = 24 + in_nc behind the stride-28 cf, the sigmoid gradient of 2
+# and 4 outputs into the stride-4 buffer, the sigma map's gradient beside 2 input channels.  The
+# seeds are the first at which the fp64 oracle's pool windows all have a winner by >= 1e-5.
+CHANNEL_CASES = [(2, 2, 2, 32, 48, 7), (1, 4, 1, 32, 48, 2), (3, 2, 1, 48, 32, 3),
+                 (2, 1, 1, 32, 32, 1)]
+
+
+@pytest.mark.parametrize("C,OC,N,H,W,seed", CHANNEL_CASES)
+def test_grads_per_tensor_vs_fp64_channel_counts(C, OC, N, H, W, seed, monkeypatch):
+    """y and every parameter tensor's gradient at in_nc 2, out_nc 2 and 4 and in_nc != out_nc,
+    against the fp64 oracle under the device's own LeakyReLU decisions: y < 1e-4 and each tensor
+    < GRAD_TOL for both arithmetics, the bf16x6 errors of the size of the fp32 kernels' own (as
+    test_x6_grads_as_accurate_as_fp32_vs_fp64)."""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.rand((N, C, H, W), generator=gen)
+    assert _pool_gap(x, C, OC) >= 1e-5
+    dy = torch.randn((N, OC, H, W), generator=gen)
+    net = _net(C, out_nc=OC).to(DEV)
+    table = iunet_ref.layer_table(C, OC)
+    errs, refs = {}, []
+    for prec in PRECS:
+        net.set_precision(prec)
+        ws = net._workspace(N, H, W, with_backward=True, fresh=True)
+        y = torch.empty((N, OC, H, W), device=DEV)
+        net._run_forward(x.to(DEV), y, ws)
+        masks = _device_leaky_masks(net, ws, x, C)
+        # the fp64 oracle under this run's LeakyReLU decisions (one reference when both agree)
+        ref = next((r for m, r in refs if all(torch.equal(a, b) for a, b in zip(m, masks))), None)
+        if ref is None:
+            mf = _MaskedF(masks)
+            monkeypatch.setattr(iunet_ref, "F", mf)
+            p = net.flat_params.cpu().double().requires_grad_(True)
+            y64 = iunet_ref.forward(p, x.double(), C, OC)
+            y64.backward(dy.double())
+            monkeypatch.undo()
+            assert not mf.masks
+            ref = (y64.detach().numpy(), p.grad.numpy())
+            refs.append((masks, ref))
+        gr = torch.full_like(net.flat_params, float("nan"))
+        net._run_backward(dy.to(DEV), gr, ws, N, H, W)
+        gr = gr.cpu().numpy()
+        off, per = 0, []
+        for _, sh in table:
+            k = int(np.prod(sh))
+            per.append(rel_err(gr[off:off + k], ref[1][off:off + k]))
+            off += k
+        assert off == gr.size
+        errs[prec] = (rel_err(y.cpu().numpy(), ref[0]), np.array(per))
+    (e32, p32), (e6, p6) = errs["fp32"], errs["fp32_x6"]
+    print(f"\n{(C, OC)} {(N, H, W)} y: fp32 {e32:.2e} x6 {e6:.2e}; grad max: fp32 {p32.max():.2e} x6 "
+          f"{p6.max():.2e}; median: fp32 {np.median(p32):.2e} x6 {np.median(p6):.2e}; "
+          f"final.weight: fp32 {p32[-2]:.2e} x6 {p6[-2]:.2e}")
+    assert e32 < FP32_TOL and e6 < FP32_TOL and e6 < 4 * e32 + 1e-7, (e6, e32)
+    bad = [(table[i][0], p32[i], p6[i]) for i in range(len(table))
+           if not (p32[i] < GRAD_TOL and p6[i] < GRAD_TOL)]
+    assert not bad, bad[:8]
     assert p6.max() < 4 * p32.max() + 1e-7, (p6.max(), p32.max())
     assert np.median(p6) < 4 * np.median(p32) + 1e-7, (np.median(p6), np.median(p32))
 

@@ -108,7 +108,7 @@ def _first_mismatch(net, ws, flat, x, C):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("C", [1, 3, 2, 4])
 def test_forward_backward_vs_reference_fixture(C, prec):
     g = np.load(os.path.join(GOLD, FIX[C]))
     flat = fixture_params(g, C)
@@ -155,7 +155,8 @@ def _check_grads(got, want, C):
 
 
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("N,C,H,W", [(1, 1, 32, 48), (2, 3, 13, 22), (1, 1, 1, 5), (3, 1, 9, 17)])
+@pytest.mark.parametrize("N,C,H,W", [(1, 1, 32, 48), (2, 3, 13, 22), (1, 1, 1, 5), (3, 1, 9, 17),
+                                     (2, 2, 13, 22), (1, 2, 32, 48), (2, 4, 13, 22), (1, 4, 32, 48)])
 def test_grads_vs_fp64_with_device_masks(N, C, H, W, prec):
     """every parameter gradient and dx against an fp64 backward that takes its LeakyReLU slopes
     from the device's own activations (only the rounding of the linear ops remains)"""
@@ -178,9 +179,20 @@ def test_large_grid_routes_vs_fp64():
     the ones of real sizes -- the Winograd kernel with its tail-packed images (48 -> 48, the
     K = 100 dec_conv1a), the 96 -> 144 data gradient in blocks of 48 behind a stride-144 mask.
     The launch records name the kernels taken; results against the fp64 restatement."""
+    _large_grid_routes_vs_fp64(1)
+
+
+def test_large_grid_routes_vs_fp64_two_channels():
+    """the same grid at in_nc = out_nc = 2: dec_conv1a's K = 98 (two live channels and two zero
+    ones in the packed tail chunk) on the Winograd kernel, the <2> thin weight gradients and
+    dL/dx, the head backward with two outputs"""
+    _large_grid_routes_vs_fp64(2)
+
+
+def _large_grid_routes_vs_fp64(C):
     from image_denoising_amd import _lib
 
-    N, C, H, W = 32, 1, 3, 250
+    N, H, W = 32, 3, 250
     net = _unit_gain(C, "fp32_x6")
     x = torch.rand(N, C, H, W, generator=torch.Generator().manual_seed(1))
     r = torch.randn(N, C, H, W, generator=torch.Generator().manual_seed(2))
@@ -192,7 +204,8 @@ def test_large_grid_routes_vs_fp64():
         _lib.profile_ops(False)
     kernels = {(q["op"], q["K"], q["NOUT"]): q["kernel"] for q in recs}
     assert kernels[("fwd3", 48, 48)] == "k_c3w6<2,48>", kernels
-    assert kernels[("fwd3", 97, 96)] == "k_c3w6<1,96>", kernels
+    assert kernels[("fwd3", 96 + C, 96)] == "k_c3w6<1,96>", kernels
+    assert {(q["K"], q["NOUT"]) for q in recs if q["op"] == "wgrad3_thin"} == {(C, 48), (C, 96)}
     assert kernels[("fwd3", 144, 96)] == "k_c3w6<2,96>", kernels
     assert kernels[("dgrad3", 96, 144)] == "k_c3w6<0,48>", kernels
     acts = _activations(net, ws, N, H, W)

@@ -147,6 +147,46 @@ def test_unsupported_config_is_an_error_not_a_fallback():
         _lib.call("dn_adam_step", None, None, None, None, 10, 1e-3, .9, .999, 1e-8, 0, 1.0, None)
 
 
+@pytest.mark.parametrize("in_nc,out_nc,names", [(5, 1, "in_nc"), (0, 1, "in_nc"), (1, 17, "out_nc"),
+                                                (2, 0, "out_nc")])
+def test_unet_channel_counts_outside_the_built_range_are_rejected(in_nc, out_nc, names):
+    """UNet takes in_nc 1..4 and out_nc 1..16: anything else is a ValueError from the
+    constructor (the library's own check, before a parameter is drawn) and DN_ERR_ARG from every
+    entry point that plans, with a message that names the argument; nothing is launched"""
+    from image_denoising_amd import UNet, _lib
+
+    with pytest.raises(ValueError, match=names):
+        UNet(in_nc=in_nc, out_nc=out_nc)
+    n = ctypes.c_size_t()
+    cfg = _lib.cfg(in_nc, out_nc, 48)
+    L = _lib.lib()
+    assert L.dn_unet_param_count(ctypes.byref(cfg), ctypes.byref(n)) == -1  # DN_ERR_ARG
+    assert names in _lib.last_error()
+    assert L.dn_unet_workspace_size(ctypes.byref(cfg), 1, 32, 32, 1, ctypes.byref(n)) == -1
+    assert names in _lib.last_error()
+    # a forward and a backward are refused by the same check before any pointer is read (the
+    # buffers are four host floats)
+    host = (ctypes.c_float * 4)()
+    buf = ctypes.addressof(host)
+    assert L.dn_unet_forward_prec(ctypes.byref(cfg), buf, buf, buf, 1, 32, 32, buf, 16, 0, None) == -1
+    assert names in _lib.last_error()
+    assert L.dn_unet_backward_prec(ctypes.byref(cfg), buf, buf, buf, buf, 1, 32, 32, buf, 16, 0,
+                                   None) == -1
+    assert names in _lib.last_error()
+
+
+@pytest.mark.parametrize("in_nc,out_nc", [(1, 1), (4, 16), (2, 5), (4, 1)])
+def test_unet_accepts_every_built_channel_count(in_nc, out_nc):
+    from image_denoising_amd import UNet
+    from image_denoising_amd.arch_unet import param_count
+
+    net = UNet(in_nc=in_nc, out_nc=out_nc)
+    assert net.flat_params.numel() == param_count(in_nc, out_nc, 48)
+    assert net.enc_conv0.weight.shape == (48, in_nc, 3, 3)
+    assert net.dec_conv1a.weight.shape == (96, 96 + in_nc, 3, 3)
+    assert net.nin_c.weight.shape == (out_nc, 96, 1, 1)
+
+
 def test_cpu_tensor_is_rejected():
     from image_denoising_amd import UNet
 

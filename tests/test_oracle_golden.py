@@ -58,28 +58,38 @@ def test_masks_one_hot_and_distinct(golden):
 
 
 # ---- U-Net init / forward / backward -------------------------------------------------------
-@pytest.mark.parametrize("C,name", [(1, "unet_c1.npz"), (3, "unet_c3.npz")])
+# (in_nc, fixture): the reference's two usual channel counts (out_nc = in_nc), then in_nc 2 and 4,
+# out_nc above 4 and in_nc != out_nc (make_golden.py unet_pairs_main: unet_c<in_nc>_<out_nc>.npz);
+# out_nc is the fixture output's channel count
+UNET_FIXTURES = [(1, "unet_c1.npz"), (3, "unet_c3.npz"), (2, "unet_c2_2.npz"),
+                 (4, "unet_c4_16.npz"), (3, "unet_c3_1.npz")]
+
+
+@pytest.mark.parametrize("C,name", UNET_FIXTURES)
 def test_reference_init_matches(golden, C, name):
     import hashlib
 
     from image_denoising_amd.arch_unet import reference_init
 
-    torch.manual_seed(0)
-    flat = reference_init(C, C, 48).numpy()
     g = golden(name)
+    torch.manual_seed(0)
+    flat = reference_init(C, g["y"].shape[1], 48).numpy()
     assert hashlib.sha256(flat.tobytes()).hexdigest() == str(g["params_sha"])
 
 
-@pytest.mark.parametrize("C,name", [(1, "unet_c1.npz"), (3, "unet_c3.npz")])
+@pytest.mark.parametrize("C,name", UNET_FIXTURES)
 def test_oracle_unet_forward_backward(golden, C, name):
     from image_denoising_amd.arch_unet import reference_init
 
     g = golden(name)
+    OC = g["y"].shape[1]
+    assert name in ("unet_c1.npz", "unet_c3.npz") or name == f"unet_c{C}_{OC}.npz"
     torch.manual_seed(0)
-    flat = reference_init(C, C, 48)
+    flat = reference_init(C, OC, 48)
     x = torch.from_numpy(g["x"]).requires_grad_(True)
     p = flat.clone().requires_grad_(True)
-    y = unet_ref.forward(p, x, C, C)
+    y = unet_ref.forward(p, x, C, OC)
+    assert y.shape == (x.shape[0], OC) + x.shape[2:]
     assert rel_err(y.detach().numpy(), g["y"]) < 1e-5
     (y ** 2).mean().backward()
     assert rel_err(x.grad.numpy(), g["dx"]) < 1e-4  # dL/dx of the reference module
@@ -90,7 +100,7 @@ def test_oracle_unet_forward_backward(golden, C, name):
         assert rel_err(grad[g["grad_idx"]], g["grad_sample"]) < 1e-4
     # per-parameter norms
     norms, off = [], 0
-    for _, ws, bl, _ in unet_ref.layer_table(C, C):
+    for _, ws, bl, _ in unet_ref.layer_table(C, OC):
         n = int(np.prod(ws))
         norms += [np.linalg.norm(grad[off:off + n]), np.linalg.norm(grad[off + n:off + n + bl])]
         off += n + bl

@@ -12,7 +12,7 @@ import resnet_ref
 from resnet_ref import FIX, GOLD, fixture_params, rel, sha, tensor_ranges
 
 
-@pytest.mark.parametrize("C", [1, 3])
+@pytest.mark.parametrize("C", [1, 3, 2, 4])
 def test_restatement_matches_reference_fixture(C):
     g = np.load(os.path.join(GOLD, FIX[C]))
     p = fixture_params(g, C).requires_grad_(True)
@@ -33,7 +33,7 @@ def test_restatement_matches_reference_fixture(C):
     np.testing.assert_allclose(norms, g["grad_norms"], rtol=1e-4, atol=1e-9)
 
 
-@pytest.mark.parametrize("C,count", [(1, 1108849), (3, 1111635)])
+@pytest.mark.parametrize("C,count", [(1, 1108849), (3, 1111635), (2, 1110242), (4, 1113028)])
 def test_module_keys_shapes_and_init_replay(C, count):
     from image_denoising_amd import RESNET, _lib
 
@@ -99,6 +99,23 @@ def test_host_side_rejections_and_any_size_workspace():
     assert "precision" in _lib.last_error()
     with pytest.raises(RuntimeError):
         RESNET(1, 1, 48)(torch.zeros(1, 1, 8, 8))
+
+
+@pytest.mark.parametrize("in_nc,out_nc,names", [(2, 3, "out_nc"), (5, 5, "in_nc"), (0, 0, "in_nc")])
+def test_channel_counts_outside_the_built_range_are_rejected(in_nc, out_nc, names):
+    """in_nc == out_nc in 1..4 is what the kernels are instantiated for: anything else is a
+    ValueError from the constructor and DN_ERR_ARG from the C-ABI's own check, whose message
+    names the argument, before any workspace is sized or anything is launched"""
+    from image_denoising_amd import RESNET, _lib
+
+    with pytest.raises(ValueError, match=names):
+        RESNET(in_nc=in_nc, out_nc=out_nc)
+    n = ctypes.c_size_t()
+    cfg = _lib.cfg(in_nc, out_nc, 48)
+    assert _lib.lib().dn_resnet_param_count(ctypes.byref(cfg), ctypes.byref(n)) == -1
+    assert names in _lib.last_error()
+    assert _lib.lib().dn_resnet_workspace_size(ctypes.byref(cfg), 1, 8, 8, 1, ctypes.byref(n)) == -1
+    assert names in _lib.last_error()
 
 
 def test_name_dispatch_builds_resnet():
