@@ -185,6 +185,8 @@ SIGNATURES = {
     "dn_adapter_slab_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "dn_adapter_backward": (c_int, [_F, _F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int,
                                     c_void_p, c_size_t, c_void_p]),
+    "dn_adapter_backward_input": (c_int, [_F, _F, _F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p]),
     "dn_finetune_loss": (c_int, [_F, _F, c_int, c_int, c_int, c_int, c_float, _F, _F, c_void_p,
                                  c_void_p]),
     "dn_iqsl_partials_size": (c_size_t, []),

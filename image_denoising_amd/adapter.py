@@ -4,7 +4,9 @@ computed by libdenoise_hip.so on gfx950.
 Same constructors, same `state_dict` keys (`adapter.net.0.weight`, ..., `base.*`), same
 forward.  The adapter's four tensors are views into ONE flat fp32 buffer (the layout
 dn_adapter_forward / dn_adapter_backward consume); the frozen base runs its own HIP forward
-under no_grad (adapter.py:59-63).
+under no_grad (adapter.py:59-63).  With freeze_base=False, use_no_grad_for_base=False the base
+trains through the adapter (adapter.py:64-66): dn_adapter_backward_input hands dL/dbase_out to
+the base's own HIP backward.
 """
 from __future__ import annotations
 
@@ -39,9 +41,19 @@ class _AdapterFunction(torch.autograd.Function):
     def backward(ctx, dout):
         noisy, base_out = ctx.saved_tensors
         mod = ctx.mod
-        dflat = torch.empty_like(mod._flat)
-        mod._run_backward(noisy, base_out, dout.contiguous(), dflat)
-        return (None, None, None, *mod._grads_from_flat(dflat, ctx.needs_input_grad[3:]))
+        dout = dout.contiguous()
+        need_noisy, need_base = ctx.needs_input_grad[0:2]
+        dnoisy = dbase = None
+        if need_noisy or need_base:  # one launch; dnoisy is formed only when asked for
+            dbase = torch.empty_like(base_out)
+            dnoisy = torch.empty_like(noisy) if need_noisy else None
+            mod._run_backward_input(noisy, base_out, dout, dbase, dnoisy)
+        pgrads = [None] * len(ctx.needs_input_grad[3:])
+        if any(ctx.needs_input_grad[3:]):
+            dflat = torch.empty_like(mod._flat)
+            mod._run_backward(noisy, base_out, dout, dflat)
+            pgrads = mod._grads_from_flat(dflat, ctx.needs_input_grad[3:])
+        return (dnoisy, dbase if need_base else None, None, *pgrads)
 
 
 class OutputAdapter(FlatParamModule):
@@ -89,13 +101,25 @@ class OutputAdapter(FlatParamModule):
                   _lib.ptr(dout), _lib.ptr(dflat), N, C, H, W, self.hidden_channels,
                   self._slab.data_ptr(), self._slab.numel(), _lib.stream_of(noisy))
 
+    def _run_backward_input(self, noisy, base_out, dout, dbase, dnoisy=None):
+        """dbase = dL/dbase_out (and dnoisy = dL/dnoisy when given) for dout = dL/dout"""
+        N, C, H, W = noisy.shape
+        _lib.call("dn_adapter_backward_input", _lib.ptr(self._flat), _lib.ptr(noisy),
+                  _lib.ptr(base_out), _lib.ptr(dout), _lib.ptr(dbase), _lib.ptr(dnoisy), N, C, H, W,
+                  self.hidden_channels, _lib.stream_of(noisy))
+
     def forward(self, noisy: torch.Tensor, base_out: torch.Tensor) -> torch.Tensor:
+        """A gradient flows into `base_out` when it requires one (the base trained through the
+        adapter) and into the parameters that require one.  `noisy` is the network's data input:
+        the module asks for no gradient with respect to it and says so (dn_adapter_backward_input
+        and _AdapterFunction compute dL/dnoisy for a caller that drives them directly)."""
         noisy, base_out = noisy.contiguous(), base_out.contiguous()
         self._check(noisy, base_out)
-        if noisy.requires_grad or base_out.requires_grad:
-            raise NotImplementedError("gradients w.r.t. the adapter inputs are not computed "
-                                      "(the reference runs the base under no_grad)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._params()):
+        if noisy.requires_grad:
+            raise NotImplementedError("the adapter module computes no gradient w.r.t. its noisy "
+                                      "input (only w.r.t. base_out and its parameters)")
+        if torch.is_grad_enabled() and (base_out.requires_grad or
+                                        any(p.requires_grad for p in self._params())):
             return _AdapterFunction.apply(noisy, base_out, self, *self._params())
         out = torch.empty_like(base_out)
         self._run_forward(noisy, base_out, out)
@@ -104,7 +128,12 @@ class OutputAdapter(FlatParamModule):
 
 class DenoiserWithAdapter(nn.Module):
     """adapter.py:29 DenoiserWithAdapter(base_model, in_channels=1, hidden_channels=16,
-    freeze_base=True, use_no_grad_for_base=True)."""
+    freeze_base=True, use_no_grad_for_base=True).
+
+    freeze_base=False, use_no_grad_for_base=False trains the base and the adapter together through
+    one loss.backward() (adapter.py:64-66): the base runs its ordinary autograd forward, in the
+    training arithmetic `set_precision` selects ('fp32' / 'fp32_x6').  The bf16 inference plan
+    (`set_inference_precision`) is forward-only and is not used on that path."""
 
     def __init__(self, base_model: nn.Module, in_channels: int = 1, hidden_channels: int = 16,
                  freeze_base: bool = True, use_no_grad_for_base: bool = True):
@@ -122,9 +151,6 @@ class DenoiserWithAdapter(nn.Module):
         if self.use_no_grad_for_base:
             with torch.no_grad():
                 base_out = self.base(x)
-        else:
-            if any(p.requires_grad for p in self.base.parameters()):
-                raise NotImplementedError("training the base through the adapter is out of scope "
-                                          "(finetune.py freezes it)")
+        else:  # adapter.py:64-66: gradients flow into the base where its parameters ask
             base_out = self.base(x)
         return self.adapter(x, base_out)

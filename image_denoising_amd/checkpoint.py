@@ -58,6 +58,17 @@ def save_adapter_checkpoint(model: torch.nn.Module, path: str) -> str:
     return save_checkpoint(model.adapter, path)
 
 
+def save_finetune_checkpoint(model: torch.nn.Module, path: str, data_parallel: bool = False) -> str:
+    """What a finetune of `model` (a DenoiserWithAdapter) has to keep.  With a trained base
+    (freeze_base=False) the base's weights moved too, so the file is the whole model's state,
+    `base.*` and `adapter.*` (finetune.py's own checkpoint; `evaluation_adapter --ckpt` and
+    `load_checkpoint(model, path)` read it back).  With a frozen base it is the adapter-only file
+    of `save_adapter_checkpoint`, to be paired with the base's own checkpoint."""
+    if getattr(model, "freeze_base", True):
+        return save_adapter_checkpoint(model, path)
+    return save_checkpoint(model, path, data_parallel=data_parallel)
+
+
 def load_adapter_checkpoint(model: torch.nn.Module, path: str):
     """evaluation_adapter_iqsl.py:90-108: an adapter-only state into `model.adapter`, non-strict;
     returns torch's (missing, unexpected)"""

@@ -6,8 +6,8 @@
 // LDS (recomputed by the backward instead of being written to HBM).  Traffic per pixel: read
 // noisy + base, write out (12*C bytes) -- HBM-bound, far below the MFMA roof.
 //
-// The backward produces only the adapter's parameter gradients (the base is frozen and run
-// under no_grad, finetune.py:255-262; the noisy input needs none): a workgroup walks a fixed
+// k_adapter_bwd produces the adapter's parameter gradients (all the frozen-base finetune needs,
+// finetune.py:255-262; k_adapter_dinput below adds the input gradients): a workgroup walks a fixed
 // set of 16x16 tiles, keeps its share of the 449 (C=1) / 1315 (C=3) parameter sums in
 // registers, writes one slab row, and the batched reduction adds the rows in a fixed order.
 //
@@ -261,6 +261,94 @@ __global__ __launch_bounds__(256, 3) void k_adapter_bwd(const float* __restrict_
     } else {
       row[A::B2 + k - T::SB - T::TB1] = acc[j][0];
     }
+  }
+}
+
+// The adapter's gradient with respect to its inputs (DenoiserWithAdapter(freeze_base=False,
+// use_no_grad_for_base=False), adapter.py:64-66: the base trains through the adapter).  With
+// x = cat[noisy, base], h = relu(conv1(x) + b1) and dout = dL/dout:
+//   dpre[h][q] = [h(q) > 0] * sum_c sum_t W2[c][h][t] * dout[c][q - (t - 1)]   (0 outside the image)
+//   dx[i][p]   = sum_h sum_t W1[h][i][t] * dpre[h][p - (t - 1)]
+//   dbase[c]   = dout[c] + dx[C + c]     (the `base_out +` of adapter.py:26)
+//   dnoisy[c]  = dx[c]                   (DN only)
+// One workgroup per 16x16 tile, k_adapter_fwd's tiling: dx at the tile's pixels needs dpre on the
+// 18^2 grid (halo 1), that needs the hidden sign there (hidden_tile from the 20^2 input tile, so
+// the recomputed bits are the forward's) and dout on the 20^2 grid (halo 2).  A thread turns the
+// hidden values it reads into dpre at the same LDS address, so dpre overlays the hidden planes
+// (pitch 18^2 = 324 floats = 4 banks past a multiple of 64: the planes of different h start on
+// different banks).  LDS: (2C + C) * 400 + 16 * 324 floats = 25,536 B at C = 1, 35,136 B at
+// C = 3 (four workgroups per CU).  Writes dbase (and dnoisy) only: no atomics, no workspace, every
+// sum one fmaf chain in a fixed order (c, t for dpre; h, t for dx), so repeats are bit-identical.
+// Traffic per pixel: read noisy, base, dout, write dbase = 16 C bytes (20 C with dnoisy).
+template <int C, bool DN>
+__global__ __launch_bounds__(256) void k_adapter_dinput(const float* __restrict__ prm,
+                                                        const float* __restrict__ noisy,
+                                                        const float* __restrict__ base,
+                                                        const float* __restrict__ dout, int N, int H,
+                                                        int W, float* __restrict__ dbase,
+                                                        float* __restrict__ dnoisy) {
+  using A = AdCfg<C>;
+  constexpr int XA = A::XE * A::XE, HA = A::HE * A::HE;
+  constexpr int I0 = DN ? 0 : C, NI = A::CI - I0;  // the input channels whose dx is wanted
+  __shared__ float sx[A::CI * XA];
+  __shared__ float sh[AD_HID * HA];  // hidden, then dpre in place
+  __shared__ float sdo[C * XA];
+  const int tid = threadIdx.x;
+  const int tiles_x = (W + AD_T - 1) / AD_T;
+  const int ty0 = (blockIdx.x / tiles_x) * AD_T, tx0 = (blockIdx.x % tiles_x) * AD_T;
+  const int n = blockIdx.y;
+  const float* pw = prm;  // scalar weight loads, as in k_adapter_bwd
+  asm volatile("" : "+s"(pw));
+  load_cat_tile<C>(noisy, base, n, H, W, ty0 - 2, tx0 - 2, sx);
+  for (int e = tid; e < C * XA; e += 256) {  // dout with a 2-pixel halo, 0 outside the image
+    const int c = e / XA, q = e - c * XA;
+    const int gy = ty0 - 2 + q / A::XE, gx = tx0 - 2 + q % A::XE;
+    sdo[e] = (gy >= 0 && gy < H && gx >= 0 && gx < W)
+                 ? dout[(((long)n * C + c) * H + gy) * W + gx] : 0.f;
+  }
+  __syncthreads();
+  hidden_tile<C>(pw, sx, H, W, ty0 - 1, tx0 - 1, sh);  // element e by thread e % 256 ...
+  // ... and so is dpre below: a thread overwrites only what it wrote itself, no barrier between
+  for (int e = tid; e < HA; e += 256) {
+    const int yy = e / A::HE, xx = e - yy * A::HE;
+    float od[C][9];  // hidden q = (yy, xx) feeds out p = q - (t/3 - 1, t%3 - 1): 20^2 grid (+1)
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) od[c][t] = sdo[c * XA + (yy + 2 - t / 3) * A::XE + xx + 2 - t % 3];
+#pragma unroll 4
+    for (int h = 0; h < AD_HID; ++h) {
+      float g = 0.f;
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int t = 0; t < 9; ++t) g = fmaf(pw[A::W2 + (c * AD_HID + h) * 9 + t], od[c][t], g);
+      const bool on = sh[h * HA + e] > 0.f;  // relu'; 0 outside the image (hidden_tile)
+      sh[h * HA + e] = on ? g : 0.f;
+    }
+  }
+  __syncthreads();
+  const int py = tid / AD_T, px = tid % AD_T;
+  const int gy = ty0 + py, gx = tx0 + px;
+  if (gy >= H || gx >= W) return;
+  float acc[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc[i] = 0.f;
+#pragma unroll 2
+  for (int h = 0; h < AD_HID; ++h) {
+    float dp[9];  // x p feeds hidden q = p - (t/3 - 1, t%3 - 1): 18^2 grid (+1)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) dp[t] = sh[h * HA + (py + 2 - t / 3) * A::HE + px + 2 - t % 3];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) acc[i] = fmaf(pw[(h * A::CI + I0 + i) * 9 + t], dp[t], acc[i]);
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const long o = (((long)n * C + c) * H + gy) * W + gx;
+    dbase[o] = sdo[c * XA + (py + 2) * A::XE + px + 2] + acc[C - I0 + c];
+    if (DN) dnoisy[o] = acc[c];
   }
 }
 
@@ -533,6 +621,29 @@ hipError_t launch_adapter_bwd(const float* prm, const float* noisy, const float*
   if (e != hipSuccess) return e;
   const long np = adapter_param_count(C);
   return launch_reduce(slab, np, nb, np, dprm, s);
+}
+
+template <int C>
+static void adapter_dinput(dim3 grid, hipStream_t s, const float* prm, const float* noisy,
+                           const float* base, const float* dout, int N, int H, int W, float* dbase,
+                           float* dnoisy) {
+  if (dnoisy)
+    hipLaunchKernelGGL((k_adapter_dinput<C, true>), grid, dim3(256), 0, s, prm, noisy, base, dout, N,
+                       H, W, dbase, dnoisy);
+  else
+    hipLaunchKernelGGL((k_adapter_dinput<C, false>), grid, dim3(256), 0, s, prm, noisy, base, dout,
+                       N, H, W, dbase, dnoisy);
+}
+
+// dnoisy may be null: then only dbase is formed and written
+hipError_t launch_adapter_dinput(const float* prm, const float* noisy, const float* base,
+                                 const float* dout, int N, int C, int H, int W, float* dbase,
+                                 float* dnoisy, hipStream_t s) {
+  const dim3 grid(((W + AD_T - 1) / AD_T) * ((H + AD_T - 1) / AD_T), N);
+  if (C == 1) adapter_dinput<1>(grid, s, prm, noisy, base, dout, N, H, W, dbase, dnoisy);
+  else if (C == 3) adapter_dinput<3>(grid, s, prm, noisy, base, dout, N, H, W, dbase, dnoisy);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
 }
 
 hipError_t launch_ft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,

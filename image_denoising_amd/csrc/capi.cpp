@@ -1023,6 +1023,21 @@ dn_status dn_adapter_backward(const float* params, const float* noisy, const flo
                     "dn_adapter_backward");
 }
 
+dn_status dn_adapter_backward_input(const float* params, const float* noisy, const float* base_out,
+                                    const float* dout, float* dbase, float* dnoisy, int N, int C,
+                                    int H, int W, int hidden_channels, void* stream) {
+  if (!params || !noisy || !base_out || !dout || !dbase) return fail(DN_ERR_ARG, "null argument");
+  if (dn_status st = adapter_args(N, C, H, W, hidden_channels)) return st;
+  // neighbouring tiles read the halo of every input: an output may overwrite none of them
+  for (const float* in : {noisy, base_out, dout})
+    if (dbase == in || dnoisy == in)
+      return fail(DN_ERR_ARG, "dbase / dnoisy must not alias noisy, base_out or dout");
+  if (dbase == dnoisy) return fail(DN_ERR_ARG, "dbase and dnoisy must be distinct buffers");
+  return hip_status(launch_adapter_dinput(params, noisy, base_out, dout, N, C, H, W, dbase, dnoisy,
+                                          (hipStream_t)stream),
+                    "dn_adapter_backward_input");
+}
+
 dn_status dn_finetune_loss(const float* pred, const float* target, int N, int C, int H, int W,
                            float lambda_grad, float* dpred, float* loss3, void* partial_ws,
                            void* stream) {

@@ -480,6 +480,9 @@ hipError_t launch_adapter_fwd(const float* prm, const float* noisy, const float*
 hipError_t launch_adapter_bwd(const float* prm, const float* noisy, const float* base,
                               const float* dout, int N, int C, int H, int W, float* dprm,
                               float* slab, hipStream_t s);
+hipError_t launch_adapter_dinput(const float* prm, const float* noisy, const float* base,
+                                 const float* dout, int N, int C, int H, int W, float* dbase,
+                                 float* dnoisy, hipStream_t s);
 hipError_t launch_ft_loss(const float* pred, const float* tgt, int N, int C, int H, int W,
                           float lam, float* dpred, float* loss3, void* partials, hipStream_t s);
 // IQSL's scalars as the kernels use them: each comparison value and centre formed in double on

@@ -9,6 +9,12 @@ OutputAdapter, trained with L1 + lambda_grad * gradient_loss on random patches.
     [data parallel: one RCCL all-reduce(sum) of the 449-float gradient]
     Adam(A, dA / world)                          dn_adam_step           (finetune.py:246-249, :288)
 
+With DenoiserWithAdapter(freeze_base=False, use_no_grad_for_base=False) the base trains too
+(FinetuneTrainer's joint step): its forward is saved, and after dA
+    dbase    = adapter input gradient(dpred)     dn_adapter_backward_input
+    dB       = base backward(dbase)              dn_<family>_backward_prec
+    Adam(B, dB / world)                          dn_adam_step
+
 No host synchronisation inside the step.  The patch loader (`DenoisePatchDataset`,
 finetune.py:100-150) is host code, as in the reference.
 """
@@ -22,11 +28,13 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import dist as dp
 from .adapter import DenoiserWithAdapter
 from .arch_unet import UNet
 from .checkpoint import strip_module_prefix
 from .flat_module import HipNet
 from .n2n import _partials_for
+from .optim import FlatAdam
 from .trainer import _FlatStepBase
 
 
@@ -279,19 +287,78 @@ class FinetuneTrainer(_AdapterStepBase):
     margin, ce_factor]) (the thresholds from `estimate_intensity_thresholds`), and the step returns
     loss4 = [loss_l1, loss_grad, loss_iqsl, loss].  Each rank's loss is the mean over its own
     batch, as an nn.DataParallel replica computes it.  guard: optim.GradGuard around the update,
-    tested against the total (the last entry)."""
+    tested against the total (the last entry).
+
+    A model built with freeze_base=False takes the joint step: the base's forward is saved
+    (set_precision's 'fp32' / 'fp32_x6' arithmetic; the bf16 inference plan is forward-only and
+    not used), dn_adapter_backward_input turns dpred into dL/dbase_out, the base's HIP backward
+    follows, and a second FlatAdam (same lr, same step count) updates the base's flat buffer
+    (`base_grad`, `base_opt`).  Every base parameter is trained.  distributed=True all-reduces
+    both gradients.  guard= is refused there (ValueError): its norm would have to span both
+    buffers (DESIGN.md)."""
 
     def __init__(self, model: DenoiserWithAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
                  distributed: bool | None = None, lambda_iqsl: float = 0.0,
                  iqsl: dict | None = None, guard=None):
         if not isinstance(model, DenoiserWithAdapter):
             raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
+        # freeze_base=False: the joint step, base and adapter trained together (adapter.py:64-66)
+        self.joint = not model.freeze_base
+        if self.joint:
+            if not isinstance(model.base, HipNet):
+                raise TypeError("the joint step needs a base of this package (UNet, RESNET, "
+                                "ImprovedUNet): it runs the base's HIP backward")
+            if guard is not None:
+                raise ValueError("guard= with a trained base is not built: the guard's gradient "
+                                 "norm would have to span both flat buffers (the base's and the "
+                                 "adapter's); train with freeze_base=True or without a guard")
         super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl, guard)
+        if self.joint:
+            # the second flat buffer: Adam is elementwise, so two FlatAdams with one lr and one
+            # step count are the reference's single Adam over every trainable parameter
+            # (finetune.py:260-263); _init_step already broadcast the base to the replicas
+            self.base_opt = FlatAdam(model.base.flat_params, lr=lr)
+            self.base_grad = torch.zeros_like(model.base.flat_params)
+
+    def _joint_buffers(self, noisy):
+        key = (tuple(noisy.shape), noisy.device, "joint")
+        if key not in self._bufs:
+            N, _, H, W = noisy.shape
+            f = dict(dtype=torch.float32, device=noisy.device)
+            self._bufs = {key: dict(
+                base=torch.empty(noisy.shape, **f), pred=torch.empty(noisy.shape, **f),
+                dbase=torch.empty(noisy.shape, **f),
+                ws=self.model.base._workspace(N, H, W, with_backward=True, fresh=True))}
+        return self._bufs[key]
+
+    def _joint_step(self, clean, noisy):
+        """base forward [saved] -> adapter -> loss -> adapter's parameter and input gradients ->
+        base backward(dbase) -> [all-reduce both gradients] -> Adam on both buffers"""
+        base, ad = self.model.base, self.model.adapter
+        base._check_input(noisy)
+        N, _, H, W = noisy.shape
+        base._check_size(H, W)
+        b = self._joint_buffers(noisy)
+        base._run_forward(noisy, b["base"], b["ws"])
+        ad._run_forward(noisy, b["base"], b["pred"])
+        loss3, dpred = self._loss(b["pred"], clean)
+        ad._run_backward(noisy, b["base"], dpred, self.grad)
+        ad._run_backward_input(noisy, b["base"], dpred, b["dbase"])
+        base._run_backward(b["dbase"], self.base_grad, b["ws"], N, H, W)
+        scale = 1.0
+        if self.distributed:
+            scale = dp.allreduce_grads(self.grad)
+            dp.allreduce_grads(self.base_grad)
+        self.opt.step(self.grad, grad_scale=scale)
+        self.base_opt.step(self.base_grad, grad_scale=scale)
+        return loss3
 
     def train_step(self, clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:
         clean, noisy = clean.contiguous(), noisy.contiguous()
         if clean.shape != noisy.shape:
             raise ValueError("clean and noisy must share one shape")
+        if self.joint:
+            return self._joint_step(clean, noisy)
         ad = self.model.adapter
         b = self._buffers(noisy.shape, noisy.device)
         self._base_forward(noisy, b["base"])

@@ -464,6 +464,15 @@ size_t dn_adapter_slab_size(int N, int C, int H, int W, int hidden_channels);
 dn_status dn_adapter_backward(const float* params, const float* noisy, const float* base_out,
                               const float* dout, float* dparams, int N, int C, int H, int W,
                               int hidden_channels, void* slab, size_t slab_bytes, void* stream);
+/* The adapter's input gradients for dout = dL/dout, for training the base through the adapter
+   (DenoiserWithAdapter(freeze_base=False, use_no_grad_for_base=False), adapter.py:64-66):
+   dbase = dL/dbase_out = dout + (conv1^T relu' conv2^T dout)[C..2C), and, when dnoisy is not null,
+   dnoisy = dL/dnoisy = the same product's channels [0..C).  Same C and hidden_channels as
+   dn_adapter_backward, any H, W >= 1.  dbase and dnoisy must not alias noisy, base_out, dout or
+   each other (DN_ERR_ARG).  Overwrites its outputs; no workspace; deterministic. */
+dn_status dn_adapter_backward_input(const float* params, const float* noisy, const float* base_out,
+                                    const float* dout, float* dbase, float* dnoisy, int N, int C,
+                                    int H, int W, int hidden_channels, void* stream);
 /* loss = L1(pred, target) + lambda_grad * gradient_loss(pred, target)  (finetune.py:283-285);
    writes dpred = dloss/dpred and loss3 = {loss_l1, loss_grad, loss}.  partial_ws holds
    dn_loss_partials_size() bytes. */
