@@ -208,6 +208,10 @@ SIGNATURES = {
                                       c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "dn_memadapter_backward": (c_int, [_F, _F, _F, _F, _F, _F, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dn_memadapter_backward_input": (c_int, [_F, _F, _F, _F, _F, _F, _F, c_int, c_int, c_int, c_int,
+                                             c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "dn_memadapter_feature_adjoint": (c_int, [_F, _F, _F, c_int, c_int, c_int, c_int, c_int,
+                                              c_void_p, c_size_t, c_void_p]),
     "dn_hann_blend": (c_int, [_F, _F, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               _F, c_void_p]),
 }

@@ -1403,7 +1403,8 @@ dn_status dn_memadapter_param_count(int in_channels, int hidden_channels, int nu
 
 size_t dn_memadapter_ws_size(int N, int C, int H, int W, int hidden_channels, int num_fft_bins,
                              int with_backward) {
-  return memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, with_backward != 0);
+  return memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins,
+                             with_backward == 2 ? 2 : with_backward != 0);
 }
 
 dn_status dn_memadapter_forward(const float* params, const float* noisy, const float* base_out,
@@ -1413,7 +1414,7 @@ dn_status dn_memadapter_forward(const float* params, const float* noisy, const f
   if (!params || !noisy || !base_out || !mem_clean || !out || !features || !ws)
     return fail(DN_ERR_ARG, "null argument");
   if (dn_status st = memadapter_args(N, C, H, W, hidden_channels, num_fft_bins)) return st;
-  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, false))
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, 0))
     return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_memadapter_ws_size()");
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const OpTimer timer(s, "memadapter_fwd", 0, 0, 0, H, W, N);
@@ -1429,13 +1430,62 @@ dn_status dn_memadapter_backward(const float* params, const float* noisy, const 
   if (!params || !noisy || !base_out || !features || !dout || !dparams || !ws)
     return fail(DN_ERR_ARG, "null argument");
   if (dn_status st = memadapter_args(N, C, H, W, hidden_channels, num_fft_bins)) return st;
-  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, true))
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, 1))
     return fail(DN_ERR_WORKSPACE, "workspace smaller than dn_memadapter_ws_size()");
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const OpTimer timer(s, "memadapter_bwd", 0, 0, 0, H, W, N);
-  return hip_status(launch_memadapter_bwd(params, noisy, base_out, features, dout, dparams, N, C, H,
-                                          W, hidden_channels, num_fft_bins, clamp_output != 0, ws, s),
+  return hip_status(launch_memadapter_bwd(params, noisy, base_out, features, dout, dparams, nullptr,
+                                          N, C, H, W, hidden_channels, num_fft_bins,
+                                          clamp_output != 0, ws, s),
                     "dn_memadapter_backward");
+}
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+static bool ranges_overlap(const void* p, size_t bytes, const void* q, size_t qbytes) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return q && a < b + qbytes && b < a + bytes;
+}
+
+dn_status dn_memadapter_backward_input(const float* params, const float* noisy,
+                                       const float* base_out, const float* features,
+                                       const float* dout, float* dparams, float* dbase, int N, int C,
+                                       int H, int W, int hidden_channels, int num_fft_bins,
+                                       int clamp_output, void* ws, size_t ws_bytes, void* stream) {
+  if (!params || !noisy || !base_out || !features || !dout || !dbase || !ws)
+    return fail(DN_ERR_ARG, "null argument");
+  if (dn_status st = memadapter_args(N, C, H, W, hidden_channels, num_fft_bins)) return st;
+  const size_t px = sizeof(float) * (size_t)N * C * H * W;
+  const size_t np = sizeof(float) * (size_t)memadapter_param_count(C, hidden_channels, num_fft_bins);
+  const size_t nf = sizeof(float) * (size_t)N * (6 + 3 * num_fft_bins);
+  if (ranges_overlap(dbase, px, params, np) || ranges_overlap(dbase, px, noisy, px) ||
+      ranges_overlap(dbase, px, base_out, px) || ranges_overlap(dbase, px, features, nf) ||
+      ranges_overlap(dbase, px, dout, px) || ranges_overlap(dbase, px, dparams, np))
+    return fail(DN_ERR_ARG, "dbase must not alias an input or dparams");
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, hidden_channels, num_fft_bins, 2))
+    return fail(DN_ERR_ARG, "workspace smaller than dn_memadapter_ws_size(with_backward = 2)");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const OpTimer timer(s, "memadapter_bwd_input", 0, 0, 0, H, W, N);
+  return hip_status(launch_memadapter_bwd(params, noisy, base_out, features, dout, dparams, dbase, N,
+                                          C, H, W, hidden_channels, num_fft_bins, clamp_output != 0,
+                                          ws, s),
+                    "dn_memadapter_backward_input");
+}
+
+dn_status dn_memadapter_feature_adjoint(const float* base_out, const float* dfeat, float* hyper,
+                                        int N, int C, int H, int W, int num_fft_bins, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  if (!base_out || !dfeat || !hyper || !ws) return fail(DN_ERR_ARG, "null argument");
+  if (dn_status st = memadapter_args(N, C, H, W, 8, num_fft_bins)) return st;
+  if (ranges_overlap(hyper, sizeof(float) * (size_t)N * C * H * W, base_out,
+                     sizeof(float) * (size_t)N * C * H * W))
+    return fail(DN_ERR_ARG, "hyper must not alias base_out");
+  if (ws_bytes < memadapter_ws_bytes(N, C, H, W, 8, num_fft_bins, 2))
+    return fail(DN_ERR_ARG, "workspace smaller than dn_memadapter_ws_size(hidden 8, with_backward = 2)");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const OpTimer timer(s, "memadapter_feat_adj", 0, 0, 0, H, W, N);
+  return hip_status(launch_memadapter_feature_adjoint(base_out, dfeat, hyper, N, C, H, W,
+                                                      num_fft_bins, ws, s),
+                    "dn_memadapter_feature_adjoint");
 }
 
 dn_status dn_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs, int ny,

@@ -513,13 +513,18 @@ hipError_t launch_mem_gather(const float* img, const MemGeom& g, const int64_t* 
                              float* out, hipStream_t s);
 bool memadapter_supported(int C, int HID, int nb);
 long memadapter_param_count(int C, int HID, int nb);
-size_t memadapter_ws_bytes(int N, int C, int H, int W, int HID, int nb, bool bwd);
+// mode: 0 forward, 1 parameter gradient, 2 parameter and input gradient
+size_t memadapter_ws_bytes(int N, int C, int H, int W, int HID, int nb, int mode);
 hipError_t launch_memadapter_fwd(const float* prm, const float* noisy, const float* base,
                                  const float* mem, float* out, float* feat, int N, int C, int H,
                                  int W, int HID, int nb, int clamp, void* ws, hipStream_t s);
 hipError_t launch_memadapter_bwd(const float* prm, const float* noisy, const float* base,
-                                 const float* feat, const float* dout, float* dprm, int N, int C,
-                                 int H, int W, int HID, int nb, int clamp, void* ws, hipStream_t s);
+                                 const float* feat, const float* dout, float* dprm, float* dbase,
+                                 int N, int C, int H, int W, int HID, int nb, int clamp, void* ws,
+                                 hipStream_t s);
+hipError_t launch_memadapter_feature_adjoint(const float* base, const float* dfeat, float* hyper,
+                                             int N, int C, int H, int W, int nb, void* ws,
+                                             hipStream_t s);
 hipError_t launch_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs,
                              int ny, int nx, int C, int H, int W, int P, float* out, hipStream_t s);
 

@@ -12,7 +12,8 @@
 //    to the lowest n.
 // 2. HyperGatedResidualAdapter(_FFT): statistics / row-DFT features (fp64), the hyper MLP, three
 //    thin 3x3 convolutions on the vector ALUs, and the parameter gradients (slab rows per
-//    workgroup, summed in a fixed order in fp64).  No atomics anywhere.
+//    workgroup, summed in a fixed order in fp64), and the gradient into base_out (direct, local
+//    and hyper routes; the hyper route is the fp64 adjoint of the features).  No atomics anywhere.
 // 3. The Hann-window blend of patchwise inference in gather form.
 #include "block_reduce.h"
 #include "dn_internal.h"
@@ -316,8 +317,39 @@ __global__ __launch_bounds__(64) void k_ma_hyper(const float* __restrict__ prm, 
   }
 }
 
+// sample b's gradients at the hyper MLP's two pre-activations: sdh[2C] (gamma | beta rows) and
+// sdk[HID] = dz0, from the tile sums part[((b * C + c) * ntiles + t) * 2 + {0, 1}] of r * dpre and
+// dpre.  Ends with a barrier; sh, sdh and sdk are then readable by every thread.
+__device__ __forceinline__ void ma_hyper_dz0(const float* __restrict__ prm, const MaLayout& L,
+                                             const float* __restrict__ f,
+                                             const float* __restrict__ gb,
+                                             const double* __restrict__ part, int ntiles, int b,
+                                             int C, int HID, float* sh, float* sdh, float* sdk) {
+  const int tid = threadIdx.x;
+  ma_mlp_hidden(prm, L, f, HID, sh);
+  if (tid < 2 * C) {
+    const int which = tid / C, c = tid - which * C;
+    const double* p = part + ((long)(b * C + c) * ntiles) * 2 + which;
+    double S = 0.0;
+    for (int t = 0; t < ntiles; ++t) S += p[2 * t];
+    if (which == 0) {
+      const float g = gb[(long)b * 3 * C + c];
+      sdh[tid] = (float)S * g * (1.f - g);
+    } else {
+      const float th = gb[(long)b * 3 * C + 2 * C + c];
+      sdh[tid] = (float)S * 0.1f * (1.f - th * th);
+    }
+  }
+  __syncthreads();
+  if (tid < HID) {
+    float a = 0.f;
+    for (int j = 0; j < 2 * C; ++j) a = fmaf(prm[L.m1w + j * HID + tid], sdh[j], a);
+    sdk[tid] = sh[tid] > 0.f ? a : 0.f;
+  }
+  __syncthreads();
+}
+
 // gradients of the hyper MLP's parameters: one workgroup walks the samples in order.
-// part[((b * C + c) * ntiles + t) * 2 + {0, 1}] = the tile's sum of r * dpre and of dpre.
 __global__ __launch_bounds__(256) void k_ma_hyper_bwd(const float* __restrict__ prm, MaLayout L,
                                                       const float* __restrict__ feat,
                                                       const float* __restrict__ gb,
@@ -330,27 +362,7 @@ __global__ __launch_bounds__(256) void k_ma_hyper_bwd(const float* __restrict__ 
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int b = 0; b < N; ++b) {
     const float* f = feat + (long)b * L.nf;
-    ma_mlp_hidden(prm, L, f, HID, sh);
-    if (tid < 2 * C) {
-      const int which = tid / C, c = tid - which * C;
-      const double* p = part + ((long)(b * C + c) * ntiles) * 2 + which;
-      double S = 0.0;
-      for (int t = 0; t < ntiles; ++t) S += p[2 * t];
-      if (which == 0) {
-        const float g = gb[(long)b * 3 * C + c];
-        sdh[tid] = (float)S * g * (1.f - g);
-      } else {
-        const float th = gb[(long)b * 3 * C + 2 * C + c];
-        sdh[tid] = (float)S * 0.1f * (1.f - th * th);
-      }
-    }
-    __syncthreads();
-    if (tid < HID) {
-      float a = 0.f;
-      for (int j = 0; j < 2 * C; ++j) a = fmaf(prm[L.m1w + j * HID + tid], sdh[j], a);
-      sdk[tid] = sh[tid] > 0.f ? a : 0.f;
-    }
-    __syncthreads();
+    ma_hyper_dz0(prm, L, f, gb, part, ntiles, b, C, HID, sh, sdh, sdk);
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int e = tid + 256 * jj;
@@ -373,12 +385,32 @@ __global__ __launch_bounds__(256) void k_ma_hyper_bwd(const float* __restrict__ 
   }
 }
 
+// dfe[b] = the gradient at base_out's features of sample b, (W0^T dz0)[2, 3, 6 + nb + k]:
+// [dmean, dstd, dphi_0 .. dphi_{nb-1}], the HID products added in order in fp64
+__global__ __launch_bounds__(64) void k_ma_hyper_dfeat(const float* __restrict__ prm, MaLayout L,
+                                                       const float* __restrict__ feat,
+                                                       const float* __restrict__ gb,
+                                                       const double* __restrict__ part, int ntiles,
+                                                       int C, int HID, int nb,
+                                                       double* __restrict__ dfe) {
+  __shared__ float sh[16], sdh[8], sdk[16];
+  const int b = blockIdx.x, j = threadIdx.x;
+  ma_hyper_dz0(prm, L, feat + (long)b * L.nf, gb, part, ntiles, b, C, HID, sh, sdh, sdk);
+  if (j >= 2 + nb) return;
+  const int col = j < 2 ? 2 + j : 6 + nb + (j - 2);
+  double a = 0.0;
+  for (int h = 0; h < HID; ++h) a += (double)prm[L.m0w + h * L.nf + col] * (double)sdk[h];
+  dfe[(long)b * (2 + MA_NBMAX) + j] = a;
+}
+
 // ---- adapter: thin 3x3 convolutions (NCHW, pad 1) ------------------------------------------------
 enum MaMode {
   MA_RELU = 0,   // out = relu(conv + bias)
   MA_MASKT = 1,  // out = aux > 0 ? convT : 0    (data gradient through a ReLU; w transposed)
   MA_FINAL = 2,  // pre = base + (gamma * (conv + bias) + beta); out = clamp ? clamp(pre) : pre
   MA_DFINAL = 3, // out = dr = gamma * dpre, part = the tile's sums of r * dpre and dpre
+  MA_DINT = 4,   // out += convT over output channels [CO, 2 CO) of w [CI][2 CO][9]: no mask (the
+                 // data gradient of local_net.0 into base_out, added to the dpre already in out)
 };
 
 struct MaConvArgs {
@@ -390,6 +422,7 @@ struct MaConvArgs {
   const float* gb;    // [N][3C]
   const float* dout;  // MA_DFINAL
   double* part;       // MA_DFINAL
+  float* dpre;        // MA_DFINAL, nullable: dpre itself (the direct route of the input gradient)
   int clamp;
 };
 
@@ -434,17 +467,20 @@ __global__ __launch_bounds__(256) void k_ma_conv(MaConvArgs a) {
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         // transposed: w is [CI][CO][9] and the taps run backwards (the data gradient)
-        const float wv = MODE == MA_MASKT ? a.w[(i * CO + o) * 9 + 8 - t] : a.w[(o * CI + i) * 9 + t];
+        const float wv = MODE == MA_MASKT  ? a.w[(i * CO + o) * 9 + 8 - t]
+                         : MODE == MA_DINT ? a.w[(i * 2 * CO + CO + o) * 9 + 8 - t]
+                                           : a.w[(o * CI + i) * 9 + t];
         acc[o] = fmaf(wv, x[t], acc[o]);
       }
   }
-  if (MODE == MA_RELU || MODE == MA_MASKT) {
+  if (MODE == MA_RELU || MODE == MA_MASKT || MODE == MA_DINT) {
     if (!in) return;
 #pragma unroll
     for (int o = 0; o < CO; ++o) {
       const long e = (((long)n * CO + o) * a.H + gy) * a.W + gx;
       if (MODE == MA_RELU) a.out[e] = fmaxf(acc[o] + a.bias[o], 0.f);
-      else a.out[e] = a.aux[e] > 0.f ? acc[o] : 0.f;
+      else if (MODE == MA_MASKT) a.out[e] = a.aux[e] > 0.f ? acc[o] : 0.f;
+      else a.out[e] = __fadd_rn(a.out[e], acc[o]);
     }
     return;
   }
@@ -462,6 +498,7 @@ __global__ __launch_bounds__(256) void k_ma_conv(MaConvArgs a) {
         dp = (!a.clamp || (pre >= 0.f && pre <= 1.f)) ? a.dout[e] : 0.f;
         rd = r * dp;
         a.out[e] = gamma * dp;
+        if (a.dpre) a.dpre[e] = dp;
       }
     }
     if (MODE == MA_DFINAL) {
@@ -561,6 +598,251 @@ __global__ __launch_bounds__(256) void k_ma_reduce(const float* __restrict__ sla
   out[e] = (float)s;
 }
 
+// ---- adapter: the hyper route of the input gradient ----------------------------------------------
+// base_out also reaches the output through its own features (mean, unbiased std, row-DFT bands),
+// which feed the hyper MLP.  Per sample, x = base_out[b] as R = C H rows of W, M = R W:
+//   A[r,f] = sum_w x[r,w] cos(2 pi f w / W),  S[r,f] = sum_w x[r,w] sin(2 pi f w / W)
+//   P_f = (1/R) sum_r (A^2 + S^2),  B_k = band mean of P_f,  L_k = log1p(B_k),  m = mean_k L_k
+//   dL_k = dphi_k / (m + eps) - (sum_j dphi_j L_j) / (nb (m + eps)^2),  dB_k = dL_k / (1 + B_k)
+//   hyper[r,w] = dmean / M + dstd (x[r,w] - mean) / ((M - 1) std)
+//              + sum_f c_f (A[r,f] cos(2 pi f w / W) + S[r,f] sin(2 pi f w / W)),
+//   c_f = dB_band(f) * 2 / (R len_band(f))          (one-sided power: DC and Nyquist take the 2 too)
+// Three launches, everything in fp64, every sum in a fixed order, one writer per element:
+//   k_ma_adj_power  a workgroup walks a fixed set of row passes: sum (x - x0), sum (x - x0)^2 and
+//                   its rows' share of every bin's power (the band powers cannot be recovered from
+//                   feat: it holds only phi_k)
+//   k_ma_adj_coef   one workgroup per sample adds the shares in order: mean, std, c of every band
+//   k_ma_adj_apply  the same row passes again: analysis A, S into LDS, then the synthesis
+// A pass stages as many rows as fit (MA_ADJ_X floats of x, MA_ADJ_F (row, bin) pairs of A and S);
+// a thread's task is one (row, bin) of the analysis and one (row, w) of the synthesis, both
+// O(W) / O(F) long.  Rows wider than MA_WMAX go one at a time with x, the twiddles and A, S in
+// global memory (WIDE).  A constant sample has std = 0 and no defined gradient (inf / nan), as in
+// the reference.
+constexpr int MA_ADJ_X = 4096;                   // floats of x staged per pass
+constexpr int MA_ADJ_F = 2 * (MA_WMAX / 2 + 1);  // (row, bin) pairs of A and of S per pass
+constexpr int MA_ADJ_CO = 4 + MA_NBMAX;          // doubles per sample: dmean/M, dstd/((M-1) std), mean, -, c_k
+constexpr int MA_ADJ_DF = 2 + MA_NBMAX;          // doubles per sample: dmean, dstd, dphi_k
+
+struct MaAdj {
+  int R, W, F, ri, iters, G;  // rows, width, bins, rows per pass, passes, workgroups per sample
+};
+
+static MaAdj ma_adj_plan(int N, int C, int H, int W) {
+  MaAdj p;
+  p.R = C * H; p.W = W; p.F = W / 2 + 1;
+  if (W > MA_WMAX) {
+    p.ri = 1;
+  } else {
+    const int a = MA_ADJ_F / p.F, b = MA_ADJ_X / W;
+    p.ri = a < b ? a : b;
+    p.ri = p.ri < p.R ? p.ri : p.R;
+  }
+  p.iters = (p.R + p.ri - 1) / p.ri;
+  int g = 1024 / N;  // about four workgroups per CU over the batch, 16 .. 256 per sample
+  g = g < 16 ? 16 : (g > 256 ? 256 : g);
+  p.G = g < p.iters ? g : p.iters;
+  return p;
+}
+
+template <bool WIDE>
+struct MaAdjLds {
+  double tw[WIDE ? 2 : 2 * MA_WMAX];
+  double as[WIDE ? 2 : 2 * MA_ADJ_F];
+  float x[WIDE ? 2 : MA_ADJ_X];
+};
+
+// A[s * F + f], S[s * F + f] of the nr rows at xs, bins f < F; T = (cos, sin)(2 pi k / W)
+__device__ __forceinline__ void ma_adj_analysis(const float* xs, int nr, int W, int F,
+                                                const double* T, double* A, double* S) {
+  for (int task = threadIdx.x; task < nr * F; task += 256) {
+    const int s = task / F, f = task - s * F;
+    const float* xr = xs + (long)s * W;
+    double re = 0.0, im = 0.0;
+    int k = 0;
+    for (int w = 0; w < W; ++w) {
+      const double v = (double)xr[w];
+      re += v * T[2 * k];
+      im += v * T[2 * k + 1];
+      k += f;
+      if (k >= W) k -= W;
+    }
+    A[task] = re;
+    S[task] = im;
+  }
+}
+
+// the pass's rows into LDS (or, WIDE, where they are) and the pointers of its A and S
+template <bool WIDE>
+__device__ __forceinline__ const float* ma_adj_stage(MaAdjLds<WIDE>& l, const float* xg, int n) {
+  if (WIDE) return xg;
+  for (int e = threadIdx.x; e < n; e += 256) l.x[e] = xg[e];
+  __syncthreads();
+  return l.x;
+}
+
+template <bool WIDE>
+__device__ __forceinline__ const double* ma_adj_twiddles(MaAdjLds<WIDE>& l, int W, int nb,
+                                                         const double* gtw) {
+  if (WIDE) return gtw;
+  if (nb > 0) {
+    for (int k = threadIdx.x; k < W; k += 256) {
+      const double a = 2.0 * (double)k / (double)W;
+      l.tw[2 * k] = cospi(a);
+      l.tw[2 * k + 1] = sinpi(a);
+    }
+    __syncthreads();
+  }
+  return l.tw;
+}
+
+// part[(b * G + g) * (2 + F)] = [sum d, sum d^2 (d = x - x[0]), the power of bins 0 .. F-1] over
+// workgroup g's passes g, g + G, ...; gas (WIDE): 2 F doubles per workgroup
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_ma_adj_power(const float* __restrict__ base, MaAdj p,
+                                                      int nb, const double* __restrict__ gtw,
+                                                      double* gas, double* part) {
+  __shared__ MaAdjLds<WIDE> l;
+  __shared__ double red[4];
+  const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x, tid = threadIdx.x;
+  const int W = p.W, F = p.F;
+  const float* x = base + (long)b * p.R * W;
+  const double x0 = (double)x[0];
+  const double* T = ma_adj_twiddles<WIDE>(l, W, nb, gtw);
+  double* A = WIDE ? gas + ((long)b * G + g) * 2 * F : l.as;
+  double* S = A + (WIDE ? F : MA_ADJ_F);
+  double* pp = part + ((long)b * G + g) * (2 + F);
+  double sd = 0.0, sdd = 0.0;
+  bool first = true;
+  for (int it = g; it < p.iters; it += G) {
+    const int r0 = it * p.ri, nr = p.R - r0 < p.ri ? p.R - r0 : p.ri;
+    const float* xs = ma_adj_stage<WIDE>(l, x + (long)r0 * W, nr * W);
+    for (int e = tid; e < nr * W; e += 256) {
+      const double d = (double)xs[e] - x0;
+      sd += d;
+      sdd += d * d;
+    }
+    if (nb > 0) {
+      ma_adj_analysis(xs, nr, W, F, T, A, S);
+      __syncthreads();
+      for (int f = tid; f < F; f += 256) {
+        double pw = 0.0;
+        for (int s = 0; s < nr; ++s) pw += A[s * F + f] * A[s * F + f] + S[s * F + f] * S[s * F + f];
+        pp[2 + f] = first ? pw : pp[2 + f] + pw;
+      }
+    }
+    first = false;
+    __syncthreads();
+  }
+  const double s0 = block_sum(sd, red);
+  const double s1 = block_sum(sdd, red);
+  if (tid == 0) {
+    pp[0] = s0;
+    pp[1] = s1;
+  }
+}
+
+// coef[b] = [dmean / M, dstd / ((M - 1) std), mean, 0, c_0 .. c_{nb-1}]; the gradient at the
+// features comes from dfd (doubles, MA_ADJ_DF per sample) or, if null, dff (floats, 2 + nb per
+// sample); pf: F doubles per sample
+__global__ __launch_bounds__(256) void k_ma_adj_coef(const float* __restrict__ base, MaAdj p, int G,
+                                                     int nb, const double* part,
+                                                     const double* __restrict__ dfd,
+                                                     const float* __restrict__ dff, double* pf,
+                                                     double* __restrict__ coef) {
+  const int b = blockIdx.x, tid = threadIdx.x, F = p.F;
+  const double* pb = part + (long)b * G * (2 + F);
+  double* P = pf + (long)b * F;
+  if (nb > 0)
+    for (int f = tid; f < F; f += 256) {
+      double s = 0.0;
+      for (int g = 0; g < G; ++g) s += pb[(long)g * (2 + F) + 2 + f];
+      P[f] = s / (double)p.R;
+    }
+  __syncthreads();
+  if (tid != 0) return;
+  const double M = (double)p.R * (double)p.W;
+  double sd = 0.0, sdd = 0.0;
+  for (int g = 0; g < G; ++g) {
+    sd += pb[(long)g * (2 + F)];
+    sdd += pb[(long)g * (2 + F) + 1];
+  }
+  const double mean = (double)base[(long)b * p.R * p.W] + sd / M;
+  const double sdev = sqrt((sdd - sd * sd / M) / (M - 1.0));
+  double df[MA_ADJ_DF];
+  for (int k = 0; k < 2 + nb; ++k)
+    df[k] = dfd ? dfd[(long)b * MA_ADJ_DF + k] : (double)dff[(long)b * (2 + nb) + k];
+  double* co = coef + (long)b * MA_ADJ_CO;
+  co[0] = df[0] / M;
+  co[1] = df[1] / ((M - 1.0) * sdev);
+  co[2] = mean;
+  co[3] = 0.0;
+  if (nb == 0) return;
+  const int bs = F / nb;
+  double Bk[MA_NBMAX], Lk[MA_NBMAX];
+  double m = 0.0, dot = 0.0;
+  for (int k = 0; k < nb; ++k) {
+    const int st = k * bs, en = k < nb - 1 ? (k + 1) * bs : F;
+    double s = 0.0;
+    for (int f = st; f < en; ++f) s += P[f];
+    Bk[k] = s / (double)(en - st);
+    Lk[k] = log1p(Bk[k]);
+    m += Lk[k];
+    dot += df[2 + k] * Lk[k];
+  }
+  m = m / (double)nb + 1e-6;
+  for (int k = 0; k < nb; ++k) {
+    const int st = k * bs, en = k < nb - 1 ? (k + 1) * bs : F;
+    const double dL = df[2 + k] / m - dot / ((double)nb * m * m);
+    co[4 + k] = dL / (1.0 + Bk[k]) * 2.0 / ((double)p.R * (double)(en - st));
+  }
+}
+
+// out[b, r, w] (+)= hyper[r, w]
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_ma_adj_apply(const float* __restrict__ base, MaAdj p,
+                                                      int nb, const double* __restrict__ gtw,
+                                                      double* gas, const double* __restrict__ coef,
+                                                      float* out, int accumulate) {
+  __shared__ MaAdjLds<WIDE> l;
+  const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x, tid = threadIdx.x;
+  const int W = p.W, F = p.F;
+  const long M = (long)p.R * W;
+  const float* x = base + (long)b * M;
+  const double* co = coef + (long)b * MA_ADJ_CO;
+  const double a0 = co[0], a1 = co[1], mean = co[2];
+  const double* T = ma_adj_twiddles<WIDE>(l, W, nb, gtw);
+  double* A = WIDE ? gas + ((long)b * G + g) * 2 * F : l.as;
+  double* S = A + (WIDE ? F : MA_ADJ_F);
+  const int bs = nb > 0 ? F / nb : 0;
+  for (int it = g; it < p.iters; it += G) {
+    const int r0 = it * p.ri, nr = p.R - r0 < p.ri ? p.R - r0 : p.ri;
+    const float* xs = ma_adj_stage<WIDE>(l, x + (long)r0 * W, nr * W);
+    if (nb > 0) {
+      ma_adj_analysis(xs, nr, W, F, T, A, S);
+      __syncthreads();
+    }
+    for (int task = tid; task < nr * W; task += 256) {
+      const int s = task / W, w = task - s * W;
+      double acc = 0.0;
+      int k = 0;
+      for (int kb = 0; kb < nb; ++kb) {
+        const int st = kb * bs, en = kb < nb - 1 ? (kb + 1) * bs : F;
+        double ab = 0.0;
+        for (int f = st; f < en; ++f) {
+          ab += A[s * F + f] * T[2 * k] + S[s * F + f] * T[2 * k + 1];
+          k += w;
+          if (k >= W) k -= W;
+        }
+        acc += co[4 + kb] * ab;
+      }
+      const double h = a0 + a1 * ((double)xs[task] - mean) + acc;
+      const long e = (long)b * M + (long)r0 * W + task;
+      out[e] = accumulate ? __fadd_rn(out[e], (float)h) : (float)h;
+    }
+    __syncthreads();
+  }
+}
+
 static int ma_tiles(int H, int W) { return ((H + MA_T - 1) / MA_T) * ((W + MA_T - 1) / MA_T); }
 
 static int ma_wg_blocks(int N, int H, int W) {
@@ -571,11 +853,14 @@ static int ma_wg_blocks(int N, int H, int W) {
 static size_t ma_align(size_t floats) { return (floats + 63) / 64 * 64; }
 
 // workspace (floats): gb | tw (doubles, W > MA_WMAX) | part (doubles) | h1 | h2 | [dr | g2 | g1 | slab]
+// and, for the input gradient (mode 2), doubles: [dfe | coef | pf | apart | gas (W > MA_WMAX)]
 struct MaWs {
-  size_t gb, tw, part, h1, h2, dr, g2, g1, slab, total;
+  size_t gb, tw, part, h1, h2, dr, g2, g1, slab, dfe, coef, pf, apart, gas, total;
 };
 
-static MaWs ma_ws(int N, int C, int H, int W, int HID, bool bwd) {
+// mode: 0 forward, 1 parameter gradient, 2 parameter and input gradient
+static MaWs ma_ws(int N, int C, int H, int W, int HID, int mode) {
+  const bool bwd = mode != 0;
   MaWs w;
   const size_t px = (size_t)N * H * W;
   size_t o = 0;
@@ -592,6 +877,15 @@ static MaWs ma_ws(int N, int C, int H, int W, int HID, bool bwd) {
     const int mc = 2 * C > HID ? 2 * C : HID;
     w.slab = o; o += ma_align((size_t)MA_WG_BLOCKS * ((size_t)HID * mc * 9 + HID));
   }
+  w.dfe = w.coef = w.pf = w.apart = w.gas = o;
+  if (mode == 2) {
+    const MaAdj p = ma_adj_plan(N, C, H, W);
+    w.dfe = o; o += ma_align((size_t)N * MA_ADJ_DF * 2);
+    w.coef = o; o += ma_align((size_t)N * MA_ADJ_CO * 2);
+    w.pf = o; o += ma_align((size_t)N * p.F * 2);
+    w.apart = o; o += ma_align((size_t)N * p.G * (2 + p.F) * 2);
+    w.gas = o; o += W > MA_WMAX ? ma_align((size_t)N * p.G * 2 * p.F * 2) : 0;
+  }
   w.total = o;
   return w;
 }
@@ -604,9 +898,9 @@ long memadapter_param_count(int C, int HID, int nb) {
   return memadapter_supported(C, HID, nb) ? ma_layout(C, HID, nb).np : -1;
 }
 
-size_t memadapter_ws_bytes(int N, int C, int H, int W, int HID, int nb, bool bwd) {
+size_t memadapter_ws_bytes(int N, int C, int H, int W, int HID, int nb, int mode) {
   if (!memadapter_supported(C, HID, nb) || N < 1 || H < 1 || W < 1) return 0;
-  return sizeof(float) * ma_ws(N, C, H, W, HID, bwd).total;
+  return sizeof(float) * ma_ws(N, C, H, W, HID, mode).total;
 }
 
 #define MA_CHECK()                        \
@@ -640,7 +934,7 @@ static hipError_t ma_fwd(const float* prm, const float* noisy, const float* base
                          float* out, float* feat, int N, int H, int W, int nb, int clamp, float* wsf,
                          hipStream_t s) {
   const MaLayout L = ma_layout(C, HID, nb);
-  const MaWs ws = ma_ws(N, C, H, W, HID, false);
+  const MaWs ws = ma_ws(N, C, H, W, HID, 0);
   const double* gtw = nullptr;
   if (nb > 0 && W > MA_WMAX) {
     double* tw = reinterpret_cast<double*>(wsf + ws.tw);
@@ -662,12 +956,48 @@ static hipError_t ma_fwd(const float* prm, const float* noisy, const float* base
   return hipGetLastError();
 }
 
+// out (+)= the hyper route: dfd (doubles, MA_ADJ_DF per sample) or dff (floats, 2 + nb per sample)
+// is the gradient at base_out's features; wsf regions tw, dfe.. of a mode-2 workspace
+static hipError_t ma_adjoint(const float* base, const double* dfd, const float* dff, float* out,
+                             int accumulate, int N, int C, int H, int W, int nb, float* wsf,
+                             const MaWs& ws, hipStream_t s) {
+  const MaAdj p = ma_adj_plan(N, C, H, W);
+  const bool wide = W > MA_WMAX;
+  double* tw = nullptr;
+  if (nb > 0 && wide) {
+    tw = reinterpret_cast<double*>(wsf + ws.tw);
+    hipLaunchKernelGGL(k_ma_twiddle, dim3((W + 255) / 256), dim3(256), 0, s, W, tw);
+    MA_CHECK();
+  }
+  double* coef = reinterpret_cast<double*>(wsf + ws.coef);
+  double* pf = reinterpret_cast<double*>(wsf + ws.pf);
+  double* apart = reinterpret_cast<double*>(wsf + ws.apart);
+  double* gas = reinterpret_cast<double*>(wsf + ws.gas);
+  const dim3 grid(p.G, N);
+  if (wide) hipLaunchKernelGGL(k_ma_adj_power<true>, grid, dim3(256), 0, s, base, p, nb, tw, gas, apart);
+  else hipLaunchKernelGGL(k_ma_adj_power<false>, grid, dim3(256), 0, s, base, p, nb, tw, gas, apart);
+  MA_CHECK();
+  hipLaunchKernelGGL(k_ma_adj_coef, dim3(N), dim3(256), 0, s, base, p, p.G, nb, apart, dfd, dff, pf,
+                     coef);
+  MA_CHECK();
+  if (wide)
+    hipLaunchKernelGGL(k_ma_adj_apply<true>, grid, dim3(256), 0, s, base, p, nb, tw, gas, coef, out,
+                       accumulate);
+  else
+    hipLaunchKernelGGL(k_ma_adj_apply<false>, grid, dim3(256), 0, s, base, p, nb, tw, gas, coef, out,
+                       accumulate);
+  return hipGetLastError();
+}
+
+// dprm (nullable) = the parameter gradient; dbase (nullable) = dpre + the data gradient of
+// local_net.0 into base_out's channels + the hyper route.  One shared chain; the launches that
+// form dprm are the same with and without dbase.
 template <int C, int HID>
 static hipError_t ma_bwd(const float* prm, const float* noisy, const float* base, const float* feat,
-                         const float* dout, float* dprm, int N, int H, int W, int nb, int clamp,
-                         float* wsf, hipStream_t s) {
+                         const float* dout, float* dprm, float* dbase, int N, int H, int W, int nb,
+                         int clamp, float* wsf, hipStream_t s) {
   const MaLayout L = ma_layout(C, HID, nb);
-  const MaWs ws = ma_ws(N, C, H, W, HID, true);
+  const MaWs ws = ma_ws(N, C, H, W, HID, dbase ? 2 : 1);
   hipError_t e = ma_features_and_convs<C, HID>(prm, L, noisy, base, feat, N, H, W, wsf, ws, s);
   if (e != hipSuccess) return e;
   const int ntiles = ma_tiles(H, W), wgb = ma_wg_blocks(N, H, W);
@@ -676,21 +1006,26 @@ static hipError_t ma_bwd(const float* prm, const float* noisy, const float* base
   float* slab = wsf + ws.slab;
   MaConvArgs a{};
   a.N = N; a.H = H; a.W = W;
-  // r, pre, dpre; dr and the (gamma, beta) sums
+  // r, pre, dpre; dr and the (gamma, beta) sums; dpre itself opens dbase
   a.in0 = wsf + ws.h2; a.c0 = HID;
   a.w = prm + L.w3; a.bias = prm + L.b3; a.out = wsf + ws.dr;
   a.aux = base; a.gb = wsf + ws.gb; a.dout = dout; a.part = part; a.clamp = clamp;
+  a.dpre = dbase;
   hipLaunchKernelGGL((k_ma_conv<HID, C, MA_DFINAL>), grid, dim3(256), 0, s, a);
   MA_CHECK();
-  hipLaunchKernelGGL(k_ma_hyper_bwd, dim3(1), dim3(256), 0, s, prm, L, feat, wsf + ws.gb, part,
-                     ntiles, N, C, HID, dprm);
-  MA_CHECK();
+  if (dprm) {
+    hipLaunchKernelGGL(k_ma_hyper_bwd, dim3(1), dim3(256), 0, s, prm, L, feat, wsf + ws.gb, part,
+                       ntiles, N, C, HID, dprm);
+    MA_CHECK();
+  }
   // layer 3: weights from (dr, h2), then the gradient into h2's pre-activation
   constexpr int ROW3 = C * HID * 9 + C, ROW2 = HID * HID * 9 + HID, ROW1 = HID * 2 * C * 9 + HID;
-  hipLaunchKernelGGL((k_ma_wgrad<HID, C>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.dr, slab);
-  MA_CHECK();
-  hipLaunchKernelGGL(k_ma_reduce, dim3((ROW3 + 255) / 256), dim3(256), 0, s, slab, ROW3, wgb, dprm + L.w3);
-  MA_CHECK();
+  if (dprm) {
+    hipLaunchKernelGGL((k_ma_wgrad<HID, C>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.dr, slab);
+    MA_CHECK();
+    hipLaunchKernelGGL(k_ma_reduce, dim3((ROW3 + 255) / 256), dim3(256), 0, s, slab, ROW3, wgb, dprm + L.w3);
+    MA_CHECK();
+  }
   MaConvArgs t{};
   t.N = N; t.H = H; t.W = W;
   t.in0 = wsf + ws.dr; t.c0 = C; t.w = prm + L.w3; t.aux = wsf + ws.h2; t.out = wsf + ws.g2;
@@ -698,19 +1033,34 @@ static hipError_t ma_bwd(const float* prm, const float* noisy, const float* base
   MA_CHECK();
   // layer 2
   a.in0 = wsf + ws.h1; a.c0 = HID;
-  hipLaunchKernelGGL((k_ma_wgrad<HID, HID>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.g2, slab);
-  MA_CHECK();
-  hipLaunchKernelGGL(k_ma_reduce, dim3((ROW2 + 255) / 256), dim3(256), 0, s, slab, ROW2, wgb, dprm + L.w2);
-  MA_CHECK();
+  if (dprm) {
+    hipLaunchKernelGGL((k_ma_wgrad<HID, HID>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.g2, slab);
+    MA_CHECK();
+    hipLaunchKernelGGL(k_ma_reduce, dim3((ROW2 + 255) / 256), dim3(256), 0, s, slab, ROW2, wgb, dprm + L.w2);
+    MA_CHECK();
+  }
   t.in0 = wsf + ws.g2; t.c0 = HID; t.w = prm + L.w2; t.aux = wsf + ws.h1; t.out = wsf + ws.g1;
   hipLaunchKernelGGL((k_ma_conv<HID, HID, MA_MASKT>), grid, dim3(256), 0, s, t);
   MA_CHECK();
   // layer 1
-  a.in0 = noisy; a.in1 = base; a.c0 = C;
-  hipLaunchKernelGGL((k_ma_wgrad<2 * C, HID>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.g1, slab);
+  if (dprm) {
+    a.in0 = noisy; a.in1 = base; a.c0 = C;
+    hipLaunchKernelGGL((k_ma_wgrad<2 * C, HID>), dim3(wgb), dim3(256), 0, s, a, wsf + ws.g1, slab);
+    MA_CHECK();
+    hipLaunchKernelGGL(k_ma_reduce, dim3((ROW1 + 255) / 256), dim3(256), 0, s, slab, ROW1, wgb, dprm + L.w1);
+    MA_CHECK();
+  }
+  if (!dbase) return hipSuccess;
+  // dbase += g1 through local_net.0's base_out channels (transposed, taps reversed, no mask)
+  t.in0 = wsf + ws.g1; t.c0 = HID; t.w = prm + L.w1; t.aux = nullptr; t.out = dbase;
+  hipLaunchKernelGGL((k_ma_conv<HID, C, MA_DINT>), grid, dim3(256), 0, s, t);
   MA_CHECK();
-  hipLaunchKernelGGL(k_ma_reduce, dim3((ROW1 + 255) / 256), dim3(256), 0, s, slab, ROW1, wgb, dprm + L.w1);
-  return hipGetLastError();
+  // dbase += the hyper route
+  double* dfe = reinterpret_cast<double*>(wsf + ws.dfe);
+  hipLaunchKernelGGL(k_ma_hyper_dfeat, dim3(N), dim3(64), 0, s, prm, L, feat, wsf + ws.gb, part,
+                     ntiles, C, HID, nb, dfe);
+  MA_CHECK();
+  return ma_adjoint(base, dfe, nullptr, dbase, 1, N, C, H, W, nb, wsf, ws, s);
 }
 
 #define MA_DISPATCH(fn, ...)                                  \
@@ -729,9 +1079,18 @@ hipError_t launch_memadapter_fwd(const float* prm, const float* noisy, const flo
 }
 
 hipError_t launch_memadapter_bwd(const float* prm, const float* noisy, const float* base,
-                                 const float* feat, const float* dout, float* dprm, int N, int C,
-                                 int H, int W, int HID, int nb, int clamp, void* ws, hipStream_t s) {
-  MA_DISPATCH(ma_bwd, prm, noisy, base, feat, dout, dprm, N, H, W, nb, clamp, static_cast<float*>(ws), s);
+                                 const float* feat, const float* dout, float* dprm, float* dbase,
+                                 int N, int C, int H, int W, int HID, int nb, int clamp, void* ws,
+                                 hipStream_t s) {
+  MA_DISPATCH(ma_bwd, prm, noisy, base, feat, dout, dprm, dbase, N, H, W, nb, clamp,
+              static_cast<float*>(ws), s);
+}
+
+hipError_t launch_memadapter_feature_adjoint(const float* base, const float* dfeat, float* hyper,
+                                             int N, int C, int H, int W, int nb, void* ws,
+                                             hipStream_t s) {
+  const MaWs w = ma_ws(N, C, H, W, 8, 2);
+  return ma_adjoint(base, nullptr, dfeat, hyper, 0, N, C, H, W, nb, static_cast<float*>(ws), w, s);
 }
 
 // ---- Hann-window blend of patchwise inference ------------------------------------------------------

@@ -234,10 +234,22 @@ def load_base_weights(model: nn.Module, ckpt_path: str):
 
 class _AdapterStepBase(_FlatStepBase):
     """What the adapter finetune steps share: the loss settings, the replicas' broadcast, Adam over
-    the adapter's flat buffer, the step's buffers and the workspace-reusing frozen-base call."""
+    the adapter's flat buffer, the step's buffers and the workspace-reusing frozen-base call; and,
+    for a model built with freeze_base=False (`joint`), the second flat buffer with its FlatAdam,
+    the joint step's buffers and the update of both."""
 
     def __init__(self, model, lr: float, lambda_grad: float, distributed: bool | None,
                  lambda_iqsl: float, iqsl: dict | None, guard=None):
+        # freeze_base=False: the joint step, base and adapter trained together (adapter.py:64-66)
+        self.joint = not model.freeze_base
+        if self.joint:
+            if not isinstance(model.base, HipNet):
+                raise TypeError("the joint step needs a base of this package (UNet, RESNET, "
+                                "ImprovedUNet): it runs the base's HIP backward")
+            if guard is not None:
+                raise ValueError("guard= with a trained base is not built: the guard's gradient "
+                                 "norm would have to span both flat buffers (the base's and the "
+                                 "adapter's); train with freeze_base=True or without a guard")
         self.model = model
         self.lambda_grad = lambda_grad
         self.lambda_iqsl = float(lambda_iqsl)
@@ -256,6 +268,12 @@ class _AdapterStepBase(_FlatStepBase):
         self._init_step(model.adapter.flat_params, lr, distributed,
                         frozen=base.flat_params.data if isinstance(base, HipNet) else None,
                         guard=guard)
+        if self.joint:
+            # the second flat buffer: Adam is elementwise, so two FlatAdams with one lr and one
+            # step count are the reference's single Adam over every trainable parameter
+            # (finetune.py:260-263); _init_step already broadcast the base to the replicas
+            self.base_opt = FlatAdam(model.base.flat_params, lr=lr)
+            self.base_grad = torch.zeros_like(model.base.flat_params)
 
     def _buffers(self, shape, device):
         key = (tuple(shape), device)
@@ -278,6 +296,38 @@ class _AdapterStepBase(_FlatStepBase):
         if self.iqsl is not None:
             return finetune_iqsl_loss(pred, clean, self.lambda_grad, self.lambda_iqsl, **self.iqsl)
         return finetune_loss(pred, clean, self.lambda_grad)
+
+    def _joint_buffers(self, noisy):
+        key = (tuple(noisy.shape), noisy.device, "joint")
+        if key not in self._bufs:
+            N, _, H, W = noisy.shape
+            f = dict(dtype=torch.float32, device=noisy.device)
+            self._bufs = {key: dict(
+                base=torch.empty(noisy.shape, **f), pred=torch.empty(noisy.shape, **f),
+                dbase=torch.empty(noisy.shape, **f),
+                ws=self.model.base._workspace(N, H, W, with_backward=True, fresh=True))}
+        return self._bufs[key]
+
+    def _joint_base_forward(self, noisy):
+        """the base's saved forward into the joint buffers"""
+        base = self.model.base
+        base._check_input(noisy)
+        N, _, H, W = noisy.shape
+        base._check_size(H, W)
+        b = self._joint_buffers(noisy)
+        base._run_forward(noisy, b["base"], b["ws"])
+        return b
+
+    def _joint_update(self, b, noisy):
+        """base backward(dbase) -> [all-reduce both gradients] -> Adam on both buffers"""
+        N, _, H, W = noisy.shape
+        self.model.base._run_backward(b["dbase"], self.base_grad, b["ws"], N, H, W)
+        scale = 1.0
+        if self.distributed:
+            scale = dp.allreduce_grads(self.grad)
+            dp.allreduce_grads(self.base_grad)
+        self.opt.step(self.grad, grad_scale=scale)
+        self.base_opt.step(self.base_grad, grad_scale=scale)
 
 
 class FinetuneTrainer(_AdapterStepBase):
@@ -302,55 +352,18 @@ class FinetuneTrainer(_AdapterStepBase):
                  iqsl: dict | None = None, guard=None):
         if not isinstance(model, DenoiserWithAdapter):
             raise TypeError("FinetuneTrainer drives a DenoiserWithAdapter")
-        # freeze_base=False: the joint step, base and adapter trained together (adapter.py:64-66)
-        self.joint = not model.freeze_base
-        if self.joint:
-            if not isinstance(model.base, HipNet):
-                raise TypeError("the joint step needs a base of this package (UNet, RESNET, "
-                                "ImprovedUNet): it runs the base's HIP backward")
-            if guard is not None:
-                raise ValueError("guard= with a trained base is not built: the guard's gradient "
-                                 "norm would have to span both flat buffers (the base's and the "
-                                 "adapter's); train with freeze_base=True or without a guard")
         super().__init__(model, lr, lambda_grad, distributed, lambda_iqsl, iqsl, guard)
-        if self.joint:
-            # the second flat buffer: Adam is elementwise, so two FlatAdams with one lr and one
-            # step count are the reference's single Adam over every trainable parameter
-            # (finetune.py:260-263); _init_step already broadcast the base to the replicas
-            self.base_opt = FlatAdam(model.base.flat_params, lr=lr)
-            self.base_grad = torch.zeros_like(model.base.flat_params)
-
-    def _joint_buffers(self, noisy):
-        key = (tuple(noisy.shape), noisy.device, "joint")
-        if key not in self._bufs:
-            N, _, H, W = noisy.shape
-            f = dict(dtype=torch.float32, device=noisy.device)
-            self._bufs = {key: dict(
-                base=torch.empty(noisy.shape, **f), pred=torch.empty(noisy.shape, **f),
-                dbase=torch.empty(noisy.shape, **f),
-                ws=self.model.base._workspace(N, H, W, with_backward=True, fresh=True))}
-        return self._bufs[key]
 
     def _joint_step(self, clean, noisy):
         """base forward [saved] -> adapter -> loss -> adapter's parameter and input gradients ->
         base backward(dbase) -> [all-reduce both gradients] -> Adam on both buffers"""
-        base, ad = self.model.base, self.model.adapter
-        base._check_input(noisy)
-        N, _, H, W = noisy.shape
-        base._check_size(H, W)
-        b = self._joint_buffers(noisy)
-        base._run_forward(noisy, b["base"], b["ws"])
+        ad = self.model.adapter
+        b = self._joint_base_forward(noisy)
         ad._run_forward(noisy, b["base"], b["pred"])
         loss3, dpred = self._loss(b["pred"], clean)
         ad._run_backward(noisy, b["base"], dpred, self.grad)
         ad._run_backward_input(noisy, b["base"], dpred, b["dbase"])
-        base._run_backward(b["dbase"], self.base_grad, b["ws"], N, H, W)
-        scale = 1.0
-        if self.distributed:
-            scale = dp.allreduce_grads(self.grad)
-            dp.allreduce_grads(self.base_grad)
-        self.opt.step(self.grad, grad_scale=scale)
-        self.base_opt.step(self.base_grad, grad_scale=scale)
+        self._joint_update(b, noisy)
         return loss3
 
     def train_step(self, clean: torch.Tensor, noisy: torch.Tensor) -> torch.Tensor:

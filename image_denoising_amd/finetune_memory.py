@@ -11,6 +11,13 @@ gradient_loss [+ lambda_iqsl * iqsl].
     [data parallel: one RCCL all-reduce(sum) of the flat gradient; every rank holds the whole bank]
     Adam(A, dA / world)                            dn_adam_step
 
+With DenoiserWithMemoryAdapter(freeze_base=False, use_no_grad_for_base=False) the base trains too
+(the joint step): its forward is saved, the selection and the gather are unchanged, and
+    dA, dbase = adapter backward(dpred)            dn_memadapter_backward_input   (one call)
+    dB        = base backward(dbase)               dn_<family>_backward_prec
+    [data parallel: both flat gradients all-reduced]
+    Adam(A, dA / world), Adam(B, dB / world)       dn_adam_step
+
 No host synchronisation inside the step.
 """
 from __future__ import annotations
@@ -24,7 +31,15 @@ from .memory import DenoiserWithMemoryAdapter
 class MemoryFinetuneTrainer(_AdapterStepBase):
     """Returns loss4 = [loss_l1, loss_grad, loss_iqsl, loss] when lambda_iqsl > 0 (`iqsl` =
     dict(t1, t2[, tau, margin, ce_factor])), else loss3 = [loss_l1, loss_grad, loss].  guard:
-    optim.GradGuard around the update, tested against the total (the last entry)."""
+    optim.GradGuard around the update, tested against the total (the last entry).
+
+    A model built with freeze_base=False takes the joint step (`joint`): the base's forward is
+    saved in `set_precision`'s 'fp32' / 'fp32_x6' arithmetic (the bf16 inference plan is
+    forward-only and not used), one dn_memadapter_backward_input call yields the adapter's
+    parameter gradient and dL/dbase_out, the base's HIP backward follows, and a second FlatAdam
+    (same lr, same step count) updates the base's flat buffer (`base_grad`, `base_opt`).
+    distributed=True all-reduces both gradients.  The base must be a HipNet (TypeError) and
+    guard= is refused there (ValueError), as in FinetuneTrainer."""
 
     def __init__(self, model: DenoiserWithMemoryAdapter, lr: float = 1e-4, lambda_grad: float = 0.1,
                  distributed: bool | None = None, lambda_iqsl: float = 0.0,
@@ -38,6 +53,14 @@ class MemoryFinetuneTrainer(_AdapterStepBase):
         if clean.shape != noisy.shape:
             raise ValueError("clean and noisy must share one shape")
         ad, bank = self.model.adapter, self.model.bank
+        if self.joint:
+            b = self._joint_base_forward(noisy)
+            mem = bank.gather_clean(bank.select(noisy))
+            feat = ad._run_forward(noisy, b["base"], mem, b["pred"])
+            loss, dpred = self._loss(b["pred"], clean)
+            ad._run_backward_input(noisy, b["base"], feat, dpred, self.grad, b["dbase"])
+            self._joint_update(b, noisy)
+            return loss
         b = self._buffers(noisy.shape, noisy.device)
         self._base_forward(noisy, b["base"])
         mem = bank.gather_clean(bank.select(noisy))

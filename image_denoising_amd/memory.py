@@ -1,7 +1,7 @@
 """The memory-conditioned adapter of the reference's finetune_memory.py /
 evaluation_704_iqsl_memory.py, computed by libdenoise_hip.so on gfx950.
 
-    base_out  = base(noisy)                       [no grad]
+    base_out  = base(noisy)                       [no grad, or trained: freeze_base=False]
     idx       = argmin_n |noisy - noise patch n|^2            dn_memory_select
     mem_clean = clean patch idx                               dn_memory_gather
     out       = HyperGatedResidualAdapter_FFT(noisy, base_out, mem_clean)   dn_memadapter_forward
@@ -10,6 +10,11 @@ The bank is IMPLICIT: a `MemoryBank` keeps the few paired images the patches are
 (megabytes), never the unfolded `[N,C,P,P]` tensors (a gigabyte each at the reference's settings);
 the selection kernel walks the windows in place.  Patch order is the reference's
 (`extract_patches` = F.unfold, images concatenated in order).
+
+With `DenoiserWithMemoryAdapter(freeze_base=False, use_no_grad_for_base=False)` the base trains
+through the adapter: dn_memadapter_backward_input hands dL/dbase_out (direct + local + hyper
+routes) to the base's own HIP backward.  The bank stays constant and the selection is an argmin:
+no gradient flows to `noisy` or `mem_clean`.
 """
 from __future__ import annotations
 
@@ -169,9 +174,22 @@ class _MemAdapterFunction(torch.autograd.Function):
     def backward(ctx, dout):
         noisy, base_out, feat = ctx.saved_tensors
         mod = ctx.mod
-        dflat = torch.empty_like(mod._flat)
-        mod._run_backward(noisy, base_out, feat, dout.contiguous(), dflat)
-        return (None, None, None, None, *mod._grads_from_flat(dflat, ctx.needs_input_grad[4:]))
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            raise NotImplementedError("no gradient w.r.t. noisy or mem_clean is computed (the bank "
+                                      "is constant and the selection is an argmin)")
+        dout = dout.contiguous()
+        need_params = any(ctx.needs_input_grad[4:])
+        dflat = torch.empty_like(mod._flat) if need_params else None
+        dbase = None
+        if ctx.needs_input_grad[1]:  # one call: dbase and, when asked for, the parameter gradient
+            dbase = torch.empty_like(base_out)
+            mod._run_backward_input(noisy, base_out, feat, dout, dflat, dbase)
+        elif need_params:
+            mod._run_backward(noisy, base_out, feat, dout, dflat)
+        pgrads = [None] * len(ctx.needs_input_grad[4:])
+        if need_params:
+            pgrads = mod._grads_from_flat(dflat, ctx.needs_input_grad[4:])
+        return (None, dbase, None, None, *pgrads)
 
 
 class HyperGatedResidualAdapter_FFT(FlatParamModule):
@@ -218,6 +236,7 @@ class HyperGatedResidualAdapter_FFT(FlatParamModule):
             raise ValueError("the row FFT has fewer bins than num_fft_bins")
 
     def _workspace(self, N, C, H, W, bwd, device):
+        """bwd: 0 / False forward, 1 / True parameter gradient, 2 parameter and input gradient"""
         need = _lib.lib().dn_memadapter_ws_size(N, C, H, W, self.hidden_channels, self.num_fft_bins,
                                                 int(bwd))
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
@@ -242,6 +261,30 @@ class HyperGatedResidualAdapter_FFT(FlatParamModule):
                   _lib.ptr(base_out), _lib.ptr(feat), _lib.ptr(dout), _lib.ptr(dflat), N, C, H, W,
                   self.hidden_channels, self.num_fft_bins, int(self.clamp_output), ws.data_ptr(),
                   ws.numel(), _lib.stream_of(noisy))
+
+    def _run_backward_input(self, noisy, base_out, feat, dout, dflat, dbase):
+        """dbase = dL/dbase_out and, unless dflat is None, dflat = dL/dparams (the bits of
+        _run_backward), in one call.  A constant base_out sample has std = 0 and no defined
+        gradient, as in the reference."""
+        N, C, H, W = noisy.shape
+        ws = self._workspace(N, C, H, W, 2, noisy.device)
+        _lib.call("dn_memadapter_backward_input", _lib.ptr(self._flat), _lib.ptr(noisy),
+                  _lib.ptr(base_out), _lib.ptr(feat), _lib.ptr(dout), _lib.ptr(dflat),
+                  _lib.ptr(dbase), N, C, H, W, self.hidden_channels, self.num_fft_bins,
+                  int(self.clamp_output), ws.data_ptr(), ws.numel(), _lib.stream_of(noisy))
+
+    def _feature_adjoint(self, base_out, dfeat) -> torch.Tensor:
+        """the hyper route alone (for tests): the adjoint of base_out's features for the cotangent
+        dfeat `[N, 2 + nb]` = (d mean, d std, d band features)"""
+        base_out, dfeat = base_out.contiguous(), dfeat.contiguous()
+        N, C, H, W = base_out.shape
+        need = _lib.lib().dn_memadapter_ws_size(N, C, H, W, 8, self.num_fft_bins, 2)
+        ws = _lib.scratch(need, base_out.device)
+        out = torch.empty_like(base_out)
+        _lib.call("dn_memadapter_feature_adjoint", _lib.ptr(base_out), _lib.ptr(dfeat),
+                  _lib.ptr(out), N, C, H, W, self.num_fft_bins, ws.data_ptr(), ws.numel(),
+                  _lib.stream_of(base_out))
+        return out
 
     def features(self, noisy, base_out, mem_clean) -> torch.Tensor:
         """the hyper MLP's input `[N, 6 + 3 nb]` (for tests)"""
@@ -273,7 +316,13 @@ class HyperGatedResidualAdapter(HyperGatedResidualAdapter_FFT):
 class DenoiserWithMemoryAdapter(nn.Module):
     """finetune_memory.py DenoiserWithMemoryAdapter.  `memory_noise_bank` is a `MemoryBank` (then
     `memory_clean_bank` is omitted) or both are `[N,C,P,P]` tensors.  The bank is no parameter and
-    no buffer: the reference's checkpoints hold `adapter.state_dict()` only."""
+    no buffer: the reference's checkpoints hold `adapter.state_dict()` only.
+
+    freeze_base=False, use_no_grad_for_base=False trains the base and the adapter together through
+    one loss.backward() (finetune_memory.py:1201-1291): the base runs its ordinary autograd
+    forward in `set_precision`'s training arithmetic, the selection stays under no_grad, and the
+    adapter's autograd function returns dL/dbase_out.  The bf16 inference plan is forward-only
+    and is not used on that path."""
 
     def __init__(self, base_model: nn.Module, in_channels: int, hidden_channels: int,
                  memory_noise_bank, memory_clean_bank=None, freeze_base: bool = True,
@@ -322,10 +371,17 @@ class DenoiserWithMemoryAdapter(nn.Module):
             with torch.no_grad():
                 base_out = self.base(noisy)
         else:
-            if any(p.requires_grad for p in self.base.parameters()):
-                raise NotImplementedError("training the base through the adapter is out of scope")
             base_out = self.base(noisy)
         mem_clean = self._select_memory_patch(noisy)
+        if torch.is_grad_enabled() and base_out.requires_grad:
+            # the base trains through the adapter.  The module's own forward refuses inputs that
+            # require grad, so enter its autograd function directly
+            ad = self.adapter
+            noisy_c, base_c = noisy.contiguous(), base_out.contiguous()
+            ad._check(noisy_c, base_c, mem_clean)
+            if noisy.requires_grad:
+                raise NotImplementedError("no gradient w.r.t. the noisy input is computed")
+            return _MemAdapterFunction.apply(noisy_c, base_c, mem_clean, ad, *ad._params())
         return self.adapter(noisy, base_out.detach(), mem_clean)
 
 

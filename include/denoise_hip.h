@@ -621,7 +621,8 @@ dn_status dn_memory_gather(const float* clean_images, const int64_t* idx, int B,
    .0.bias, hyper_mlp.2.weight [2C, Hc], .2.bias.  C is 1 or 3, Hc 8 or 16, nb <= 8. */
 dn_status dn_memadapter_param_count(int in_channels, int hidden_channels, int num_fft_bins,
                                     size_t* count);
-/* bytes of workspace of the forward (with_backward = 0) or the backward (0 = unsupported) */
+/* bytes of workspace of the forward (with_backward = 0), of dn_memadapter_backward (1) or of
+   dn_memadapter_backward_input (2, at least 1's); 0 = unsupported */
 size_t dn_memadapter_ws_size(int N, int C, int H, int W, int hidden_channels, int num_fft_bins,
                              int with_backward);
 /* features [N, 6 + 3 nb] = mean / unbiased std of noisy, base_out, mem_clean, then their row-DFT
@@ -637,6 +638,26 @@ dn_status dn_memadapter_backward(const float* params, const float* noisy, const 
                                  const float* features, const float* dout, float* dparams, int N,
                                  int C, int H, int W, int hidden_channels, int num_fft_bins,
                                  int clamp_output, void* ws, size_t ws_bytes, void* stream);
+/* dbase = dL/dbase_out for dout = dL/dout: dpre (dout masked by the clamp) + the data gradient of
+   local_net.0 into base_out's channels + the hyper route (base_out's mean, unbiased std and
+   row-DFT band features feed gamma and beta).  dparams is nullable; when given it receives exactly
+   the bits dn_memadapter_backward writes for the same inputs.  One pass over the shared chain;
+   fp64 statistics and DFT sums, fixed summation order, no atomics, bit-identical from run to run.
+   DN_ERR_ARG: a null dbase, a dbase that overlaps an input or dparams, an unsupported C / hidden /
+   num_fft_bins, a workspace below dn_memadapter_ws_size(..., 2).  A constant base_out sample has
+   std = 0 and no defined gradient (inf / nan), as in torch.  No gradient w.r.t. noisy or
+   mem_clean is formed. */
+dn_status dn_memadapter_backward_input(const float* params, const float* noisy,
+                                       const float* base_out, const float* features,
+                                       const float* dout, float* dparams, float* dbase, int N, int C,
+                                       int H, int W, int hidden_channels, int num_fft_bins,
+                                       int clamp_output, void* ws, size_t ws_bytes, void* stream);
+/* The hyper route alone (introspection / tests): hyper [N,C,H,W] = the adjoint of base_out's
+   features for the cotangent dfeat [N, 2 + nb] = (d mean, d std, d band feature 0 .. nb-1).
+   ws: dn_memadapter_ws_size(N, C, H, W, 8, nb, 2) bytes. */
+dn_status dn_memadapter_feature_adjoint(const float* base_out, const float* dfeat, float* hyper,
+                                        int N, int C, int H, int W, int num_fft_bins, void* ws,
+                                        size_t ws_bytes, void* stream);
 /* Patchwise inference's blend: pred [ny * nx, C, P, P] are the patches at origins (ys[iy], xs[ix])
    (device int32), hann the 1-D window [P]; out [C, H, W] = sum pred * w / (sum w + 1e-8), w =
    max(hann[py] * hann[px], 1e-3), each pixel's patches added in the order iy, ix. */
