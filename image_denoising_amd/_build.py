@@ -20,8 +20,9 @@ TAG = os.environ.get("DN_BUILD_TAG", "")
 BUILD = os.path.join(PKG, "_objs" + (f"_{TAG}" if TAG else ""))
 LIB = os.path.join(PKG, "libdenoise_hip" + (f"_{TAG}" if TAG else "") + ".so")
 SOURCES = ["conv.hip", "conv_bf16.hip", "conv_x6.hip", "head_x6.hip", "deconv_x6.hip", "upconv_x6.hip", "conv_w6.hip", "wgrad_x6p.hip", "elementwise.hip", "guard.hip", "first_layer.hip", "eval.hip", "adapter.hip", "memory.hip", "fft_loss.hip", "iunet_ops.hip", "wgrad_route.cpp", "exec_common.cpp", "unet.cpp",
-           "iunet.cpp", "resnet.cpp", "capi.cpp", "profile.cpp"]
-HEADERS = ["dn_internal.h", "wgrad_route.h", "block_reduce.h", "conv_epi.h", "x6_core.h", "x6_tile.h", "philox.h", "exec_common.h", "unet.h", "iunet.h", "iunet_ops.h", "resnet.h"]
+           "iunet.cpp", "resnet.cpp", "capi_net.cpp", "capi_train.cpp", "capi_ops.cpp", "capi_blocks.cpp",
+           "capi_eval.cpp", "capi_adapter.cpp", "profile.cpp"]
+HEADERS = ["dn_internal.h", "wgrad_route.h", "block_reduce.h", "conv_epi.h", "x6_core.h", "x6_tile.h", "philox.h", "exec_common.h", "capi_common.h", "unet.h", "iunet.h", "iunet_ops.h", "resnet.h"]
 ARCH = os.environ.get("DN_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",

@@ -39,6 +39,19 @@ class DnGuardStats(ctypes.Structure):  # include/denoise_hip.h dn_guard_stats
 _F = c_void_p  # float*  (device)
 _U8 = c_void_p  # uint8_t* (device)
 
+# the argument lists the network families share (dn_<family>_*)
+_CFG = POINTER(DnCfg)
+_NHW = [c_int, c_int, c_int]
+_WS = [c_void_p, c_size_t]  # workspace, its size in bytes
+_PARAM_COUNT = [_CFG, POINTER(c_size_t)]
+_PARAM_INFO = [_CFG, c_int, POINTER(c_size_t), POINTER(c_size_t), POINTER(c_size_t)]
+_WORKSPACE_SIZE = [_CFG, *_NHW, c_int, POINTER(c_size_t)]  # ..., with_backward, bytes
+_FORWARD = [_CFG, _F, _F, _F, *_NHW, *_WS, c_void_p]  # cfg, params, x, y, ..., stream
+_FORWARD_PREC = [*_FORWARD[:-1], c_int, c_void_p]  # ..., precision, stream
+_BACKWARD = [_CFG, _F, _F, _F, _F, *_NHW, *_WS, c_void_p]  # cfg, params, dy, dparams, dx, ...
+_BACKWARD_PREC = [*_BACKWARD[:-1], c_int, c_void_p]
+_DEBUG_BUFFERS = [_CFG, *_NHW, c_int, POINTER(c_int64), c_int, POINTER(c_int)]
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "dn_version": (c_char_p, []),
@@ -47,43 +60,27 @@ SIGNATURES = {
     "dn_prepare_streams": (c_int, [c_void_p]),
     "dn_profile_ops_read": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "dn_last_error": (c_int, [c_char_p, c_size_t]),
-    "dn_unet_param_count": (c_int, [POINTER(DnCfg), POINTER(c_size_t)]),
-    "dn_unet_param_info": (c_int, [POINTER(DnCfg), c_int, POINTER(c_size_t), POINTER(c_size_t),
-                                   POINTER(c_size_t)]),
-    "dn_unet_workspace_size": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                       POINTER(c_size_t)]),
-    "dn_unet_forward": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                c_size_t, c_void_p]),
-    "dn_unet_backward": (c_int, [POINTER(DnCfg), _F, _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                 c_size_t, c_void_p]),
-    "dn_unet_forward_bf16": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                     c_size_t, c_void_p]),
+    "dn_unet_param_count": (c_int, _PARAM_COUNT),
+    "dn_unet_param_info": (c_int, _PARAM_INFO),
+    "dn_unet_workspace_size": (c_int, _WORKSPACE_SIZE),
+    "dn_unet_forward": (c_int, _FORWARD),
+    "dn_unet_backward": (c_int, _BACKWARD),
+    "dn_unet_forward_bf16": (c_int, _FORWARD),
     "dn_unet_forward_n2n": (c_int, [POINTER(DnCfg), _F, _F, _F, _U8, c_int, c_int, c_int,
                                     c_void_p, c_size_t, c_int, c_void_p]),
-    "dn_unet_forward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                     c_size_t, c_int, c_void_p]),
+    "dn_unet_forward_prec": (c_int, _FORWARD_PREC),
     "dn_unet_pack_weights": (c_int, [POINTER(DnCfg), _F, c_int, c_int, c_int, c_void_p, c_size_t,
                                      c_int, c_void_p]),
-    "dn_unet_forward_prepacked": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int,
-                                          c_void_p, c_size_t, c_int, c_void_p]),
-    "dn_unet_backward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, _F, c_int, c_int, c_int,
-                                      c_void_p, c_size_t, c_int, c_void_p]),
-    "dn_unet_backward_split": (c_int, [POINTER(DnCfg), _F, _F, _F, _F, c_int, c_int, c_int,
-                                       c_void_p, c_size_t, c_int, c_void_p, c_void_p,
-                                       POINTER(c_int64)]),
-    "dn_unet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                      POINTER(c_int64), c_int, POINTER(c_int)]),
-    "dn_resnet_param_count": (c_int, [POINTER(DnCfg), POINTER(c_size_t)]),
-    "dn_resnet_param_info": (c_int, [POINTER(DnCfg), c_int, POINTER(c_size_t), POINTER(c_size_t),
-                                     POINTER(c_size_t)]),
-    "dn_resnet_workspace_size": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                         POINTER(c_size_t)]),
-    "dn_resnet_forward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                       c_size_t, c_int, c_void_p]),
-    "dn_resnet_backward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, _F, c_int, c_int, c_int,
-                                        c_void_p, c_size_t, c_int, c_void_p]),
-    "dn_resnet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                        POINTER(c_int64), c_int, POINTER(c_int)]),
+    "dn_unet_forward_prepacked": (c_int, _FORWARD_PREC),
+    "dn_unet_backward_prec": (c_int, _BACKWARD_PREC),
+    "dn_unet_backward_split": (c_int, [*_BACKWARD_PREC, c_void_p, POINTER(c_int64)]),
+    "dn_unet_debug_buffers": (c_int, _DEBUG_BUFFERS),
+    "dn_resnet_param_count": (c_int, _PARAM_COUNT),
+    "dn_resnet_param_info": (c_int, _PARAM_INFO),
+    "dn_resnet_workspace_size": (c_int, _WORKSPACE_SIZE),
+    "dn_resnet_forward_prec": (c_int, _FORWARD_PREC),
+    "dn_resnet_backward_prec": (c_int, _BACKWARD_PREC),
+    "dn_resnet_debug_buffers": (c_int, _DEBUG_BUFFERS),
     "dn_n2n_subsample": (c_int, [_F, c_int, c_int, c_int, c_int, _U8, c_uint64, c_uint64, c_uint64,
                                  _F, _F, _U8, c_void_p]),
     "dn_n2n_masks": (c_int, [_U8, c_int64, _U8, _U8, c_void_p]),
@@ -156,19 +153,14 @@ SIGNATURES = {
     "dn_ssim_u8": (c_int, [_U8, _U8, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dn_l1_mean_batched": (c_int, [_F, _F, c_int64, c_int64, c_void_p, c_void_p]),
     "dn_l1_mean": (c_int, [_F, _F, c_int64, c_void_p, c_void_p, c_void_p]),
-    "dn_iunet_param_count": (c_int, [POINTER(DnCfg), POINTER(c_size_t)]),
-    "dn_iunet_workspace_size": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                        POINTER(c_size_t)]),
-    "dn_iunet_forward": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                 c_size_t, c_void_p]),
-    "dn_iunet_backward": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                  c_size_t, c_void_p]),
-    "dn_iunet_forward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                      c_size_t, c_int, c_void_p]),
-    "dn_iunet_backward_prec": (c_int, [POINTER(DnCfg), _F, _F, _F, c_int, c_int, c_int, c_void_p,
-                                       c_size_t, c_int, c_void_p]),
-    "dn_iunet_debug_buffers": (c_int, [POINTER(DnCfg), c_int, c_int, c_int, c_int,
-                                       POINTER(c_int64), c_int, POINTER(c_int)]),
+    "dn_iunet_param_count": (c_int, _PARAM_COUNT),
+    "dn_iunet_workspace_size": (c_int, _WORKSPACE_SIZE),
+    "dn_iunet_forward": (c_int, _FORWARD),
+    # (ImprovedUNet's backward has no dx: cfg, params, dy, dparams, ... as a forward's list)
+    "dn_iunet_backward": (c_int, _FORWARD),
+    "dn_iunet_forward_prec": (c_int, _FORWARD_PREC),
+    "dn_iunet_backward_prec": (c_int, _FORWARD_PREC),
+    "dn_iunet_debug_buffers": (c_int, _DEBUG_BUFFERS),
     "dn_groupnorm_scratch_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dn_groupnorm_forward": (c_int, [_F, c_int, c_int, _F, c_int, c_int, _F, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_int, _F, _F, c_int, _F, c_void_p,

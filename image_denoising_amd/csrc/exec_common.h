@@ -2,6 +2,7 @@
 // the backward's streams, the op helpers, and what the UNet and the RESNET have in common (slab
 // plan, 3x3 data-gradient routes, dec_conv1a's weight gradient, the nin head): exec_common.cpp.
 #pragma once
+#include <functional>
 #include <string>
 
 #include "../../include/denoise_hip.h"
@@ -27,6 +28,10 @@ extern thread_local std::string g_last_error;
     const ::dn::OpTimer dn_timer_(st, op, flops, K, NO, h, w, n); \
     DN_TRY(call);                                             \
   } while (0)
+
+// what a plan's *_debug_buffers hands out per activation / gradient buffer: offset in floats,
+// pixel stride in channels, resolution level
+using BufferVisitor = std::function<void(long off, int stride, int level)>;
 
 struct Layer {
   int cout, cin, k;

@@ -186,7 +186,7 @@ struct Alloc {
 
 }  // namespace
 
-// ---- GroupNorm and the blocked weight gradient: launch sequences shared with capi.cpp ------
+// ---- GroupNorm and the blocked weight gradient: launch sequences shared with capi_blocks.cpp
 long gn_part_doubles(int N, long P, int C) { return 2L * N * chan_sums_splits(N, P) * C; }
 
 dn_status gn_forward(const View& z, int N, long P, int C, int G, const float* gamma,
@@ -435,6 +435,28 @@ bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan
   }
   p.total_floats = off;
   return true;
+}
+
+void iunet_debug_buffers(const IPlan& p, const BufferVisitor& add) {
+  auto blk = [&](const IBlockBufs& b, int ch, int l) {
+    add(b.F, ch + 128, l); add(b.r, ch, l); add(b.z1, ch, l); add(b.a1, ch, l); add(b.z2, ch, l);
+  };
+  add(p.x0, 4, 0); add(p.h, 48, 0);
+  for (int i = 0; i < 4; ++i) blk(p.dl[i], 48 << i, i);
+  blk(p.bb, 384, 4);
+  for (int k = 0; k < 4; ++k) {
+    const int out = p.P.up[k].out;
+    add(p.cc[k], 3 * out, 3 - k);
+    blk(p.ul[k], out, 3 - k);
+  }
+  add(p.xb, 384, 4); add(p.cf, 28, 0);
+  if (!p.with_bwd) return;
+  for (int i = 0; i < 4; ++i) {
+    const int ch = 48 << i;
+    add(p.dl[i].dr, ch, i); add(p.dl[i].dz2, ch, i); add(p.dl[i].dg1, ch, i);
+    add(p.dl[i].dz1, ch, i);
+  }
+  for (int k = 0; k < 4; ++k) add(p.dcc[k], 3 * p.P.up[k].out, 3 - k);
 }
 
 // ------------------------------------------------------------------------------------

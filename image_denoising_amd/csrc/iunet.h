@@ -2,8 +2,7 @@
 #pragma once
 #include <string>
 
-#include "../../include/denoise_hip.h"
-#include "dn_internal.h"
+#include "exec_common.h"
 
 namespace dn {
 
@@ -82,7 +81,7 @@ struct IPlan {
   long total_floats = 0;
 };
 
-// ---- launch sequences the executor shares with the op-level entry points (capi.cpp) --------
+// ---- launch sequences the executor shares with the op-level entry points (capi_blocks.cpp) -
 // GroupNorm(G groups of C channels, eps 1e-5) over N x P pixels of NHWC views.  part holds
 // gn_part_doubles(N, P, C) doubles, every coefficient array N * C floats (16-byte aligned).
 // Forward: stats [N][G] (mean, rstd) saved, y = [res +] [leaky](z * scale + shift).
@@ -98,6 +97,10 @@ dn_status gn_backward(const View& dy, const View& z, int N, long P, int C, int G
 bool iunet_build_params(const dn_unet_cfg& c, IParams& P, std::string& err);
 bool iunet_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, IPlan& p,
                       std::string& err);
+// dn_iunet_debug_buffers' list: the main activations, in the order
+//   x0 h | per down level i: F r z1 a1 z2 | bottle: F r z1 a1 z2 | per up k: cc F r z1 a1 z2 | xb cf
+//   | with a backward: per down level: dr dz2 dg1 dz1 | per up k: dcc
+void iunet_debug_buffers(const IPlan& p, const BufferVisitor& add);
 // prec: DN_PREC_FP32, or DN_PREC_FP32_X6 (the 3x3 convs' forward and data gradient as split
 // bf16 products, conv_x6.hip)
 dn_status iunet_forward(const IPlan& p, const float* prm, const float* x, float* y, float* ws,

@@ -9,8 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "denoise_hip.h"
-#include "dn_internal.h"
+#include "capi_common.h"
 
 namespace dn {
 
@@ -75,35 +74,39 @@ static void clear_locked() {
 extern "C" {
 
 dn_status dn_profile_ops(int enable) {
-  std::lock_guard<std::mutex> lock(dn::g_mu);
-  dn::clear_locked();
-  dn::g_on = enable != 0;
-  return DN_OK;
+  return dn::guarded([&] {
+    std::lock_guard<std::mutex> lock(dn::g_mu);
+    dn::clear_locked();
+    dn::g_on = enable != 0;
+    return DN_OK;
+  });
 }
 
 dn_status dn_profile_ops_read(dn_op_record* out, int cap, int* count) {
-  if (!count || (cap > 0 && !out)) return DN_ERR_ARG;
-  std::lock_guard<std::mutex> lock(dn::g_mu);
-  int n = 0;
-  dn_status st = DN_OK;
-  for (const dn::Rec& r : dn::g_recs) {
-    if (hipEventSynchronize(r.b) != hipSuccess) { st = DN_ERR_HIP; break; }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) { st = DN_ERR_HIP; break; }
-    if (n < cap) {
-      dn_op_record& o = out[n];
-      std::memset(&o, 0, sizeof o);
-      std::snprintf(o.op, sizeof o.op, "%s", r.op);
-      std::snprintf(o.kernel, sizeof o.kernel, "%s", r.kernel);
-      o.K = r.K; o.NOUT = r.NOUT; o.H = r.H; o.W = r.W; o.N = r.N;
-      o.flops = r.flops;
-      o.ms = ms;
+  return dn::guarded([&] {
+    if (!count || (cap > 0 && !out)) return DN_ERR_ARG;
+    std::lock_guard<std::mutex> lock(dn::g_mu);
+    int n = 0;
+    dn_status st = DN_OK;
+    for (const dn::Rec& r : dn::g_recs) {
+      if (hipEventSynchronize(r.b) != hipSuccess) { st = DN_ERR_HIP; break; }
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) { st = DN_ERR_HIP; break; }
+      if (n < cap) {
+        dn_op_record& o = out[n];
+        std::memset(&o, 0, sizeof o);
+        std::snprintf(o.op, sizeof o.op, "%s", r.op);
+        std::snprintf(o.kernel, sizeof o.kernel, "%s", r.kernel);
+        o.K = r.K; o.NOUT = r.NOUT; o.H = r.H; o.W = r.W; o.N = r.N;
+        o.flops = r.flops;
+        o.ms = ms;
+      }
+      ++n;
     }
-    ++n;
-  }
-  *count = n;
-  dn::clear_locked();
-  return st;
+    *count = n;
+    dn::clear_locked();
+    return st;
+  });
 }
 
 }  // extern "C"

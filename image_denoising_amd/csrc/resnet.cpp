@@ -165,6 +165,23 @@ bool res_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, ResPlan
   return true;
 }
 
+void resnet_debug_buffers(const ResPlan& p, const BufferVisitor& add_at) {
+  const auto add = [&](long off, int stride) { add_at(off, stride, 0); };
+  const int nf = p.nf;
+  add(p.c1, p.c1s); add(p.a0, nf);
+  for (int k = 2; k <= 5; ++k) add(p.c[k], p.cs[k]);
+  add(p.a5, nf);
+  for (int k = 2; k <= 5; ++k) add(p.da[k], 2 * nf);
+  add(p.d1a, 96); add(p.d1b, 96);
+  if (!p.with_bwd) return;
+  add(p.na, 96); add(p.nb, 96);
+  add(p.g_na, 96); add(p.g_d1b, 96); add(p.g_d1a, 96); add(p.g_c1, 2 * nf);
+  for (int k = 2; k <= 5; ++k) add(p.g_c[k], p.cs[k]);
+  for (int k = 2; k <= 5; ++k) add(p.g_da[k], 2 * nf);
+  for (int j = 1; j <= 4; ++j) add(p.g_a[j], nf);
+  add(p.g_a5, nf); add(p.g_a0, nf);
+}
+
 // ------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------

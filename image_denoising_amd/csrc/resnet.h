@@ -55,6 +55,9 @@ const char* res_layer_name(int i);
 bool res_build_params(const dn_unet_cfg& c, ResParamLayout& P, std::string& err);
 bool res_build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, ResPlan& p,
                     std::string& err);
+// dn_resnet_debug_buffers' list (every level 0), in order: c1 a0 c2 c3 c4 c5 a5 d2a d3a d4a d5a d1a
+// d1b | with a backward: na nb g_na g_d1b g_d1a g_c1 g_c2..g_c5 g_d2a..g_d5a g_a1..g_a4 g_a5 g_a0
+void resnet_debug_buffers(const ResPlan& p, const BufferVisitor& add);
 // prec: DN_PREC_FP32 or DN_PREC_FP32_X6
 dn_status resnet_forward(const ResPlan& p, const float* prm, const float* x, float* y, float* ws,
                          hipStream_t s, int prec);

@@ -236,6 +236,25 @@ bool build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, Plan& p, st
   return true;
 }
 
+void unet_debug_buffers(const Plan& p, const BufferVisitor& add) {
+  const int nf = p.nf;
+  add(p.c1, p.c1s, 0); add(p.a0, nf, 0); add(p.a1, nf, 0);
+  for (int l = 1; l <= 4; ++l) add(p.c[l], p.cs[l], l);
+  for (int l = 1; l <= 4; ++l) add(p.a[l], nf, l);
+  add(p.p5, nf, 5); add(p.a6, nf, 5);
+  for (int l = 1; l <= 4; ++l) add(p.da[l], 2 * nf, l);
+  for (int l = 1; l <= 4; ++l) add(p.db[l], 2 * nf, l);
+  add(p.d1a, 96, 0); add(p.d1b, 96, 0); add(p.na, 96, 0); add(p.nb, 96, 0);
+  if (!p.with_bwd) return;
+  add(p.g_nb, 96, 0); add(p.g_na, 96, 0); add(p.g_d1b, 96, 0); add(p.g_d1a, 96, 0);
+  add(p.g_c1, 2 * nf, 0);
+  for (int l = 1; l <= 4; ++l) add(p.g_c[l], p.cs[l], l);
+  for (int l = 1; l <= 4; ++l) add(p.g_da[l], 2 * nf, l);
+  for (int l = 1; l <= 4; ++l) add(p.g_db[l], 2 * nf, l);
+  for (int l = 1; l <= 4; ++l) add(p.g_a[l], nf, l);
+  add(p.g_a6, nf, 5); add(p.g_p5, nf, 5); add(p.g_a0, nf, 0); add(p.g_a1, nf, 0);
+}
+
 // channels of the data gradient a layer's backward must produce
 int dgrad_nout(const Plan& p, int i) {
   if (i == D1A) return 2 * p.nf;  // only the up1 part of [up1 | x]

@@ -62,6 +62,10 @@ int layer_level(int i);
 int dgrad_nout(const Plan& p, int i);
 bool build_params(const dn_unet_cfg& c, ParamLayout& P, std::string& err);
 bool build_plan(const dn_unet_cfg& c, int N, int H, int W, bool bwd, Plan& p, std::string& err);
+// dn_unet_debug_buffers' list, in order: c1 a0 a1 c[1..4] a[1..4] p5 a6 da[1..4] db[1..4] d1a d1b
+// na nb | with a backward: g_nb g_na g_d1b g_d1a g_c1 g_c[1..4] g_da[1..4] g_db[1..4] g_a[1..4]
+// g_a6 g_p5 g_a0 g_a1
+void unet_debug_buffers(const Plan& p, const BufferVisitor& add);
 // prec: DN_PREC_FP32 (fp32 matrix cores), DN_PREC_FP32_X6 (3x3 layers on the bf16 matrix cores
 // by three-way operand splitting, fp32-accurate), DN_PREC_BF16 (forward only, bf16 operands)
 // sel_rd (nullable, DN_PREC_FP32_X6 and no backward only): dec_conv1b and the head run on the
