@@ -49,9 +49,13 @@ dn_status dn_conv2d_forward(const float* x, int x_stride, int N, int H, int W, i
     hipStream_t s = (hipStream_t)stream;
     float* wp = static_cast<float*>(pack_ws);
     hipError_t e = pack_conv_fwd(w, Cin, Cout, ksize, wp, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess) {
+      // (dn_profile_ops: the record brackets the GEMM launch alone, so its label is the GEMM's)
+      const OpTimer timer(s, ksize == 3 ? "fwd3" : "fwd1",
+                          2.0 * Cin * Cout * ksize * ksize * N * H * W, Cin, Cout, H, W, N);
       e = conv_forward(View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cin, wp, b, Cout, ksize,
                        act, View{y, y_stride, 0}, OUT_NHWC, s);
+    }
     return hip_status(e, "dn_conv2d_forward");
   });
 }
@@ -80,6 +84,7 @@ dn_status dn_conv2d_forward_bf16(const float* x, int x_stride, int N, int H, int
       FwdArgs a = fwd_args(View{const_cast<float*>(x), x_stride, 0}, N, H, W, Cin, Cout,
                            View{y, y_stride, 0}, OUT_NHWC);
       a.wp = static_cast<const float*>(pack_ws); a.bias = b; a.epi = act ? EPI_BIAS_ACT : EPI_BIAS;
+      const OpTimer timer(s, "fwd3", 2.0 * Cin * Cout * 9 * N * H * W, Cin, Cout, H, W, N);
       e = launch_fwd_bf16(a, s);
     }
     return hip_status(e, "dn_conv2d_forward_bf16");
@@ -201,9 +206,12 @@ dn_status dn_conv2d_backward_data(const float* dz, int N, int H, int W, int Cout
     hipStream_t s = (hipStream_t)stream;
     float* wp = static_cast<float*>(pack_ws);
     hipError_t e = pack_conv_dgrad(w, Cin, Cin, Cout, ksize, wp, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess) {
+      const OpTimer timer(s, ksize == 3 ? "dgrad3" : "dgrad1",
+                          2.0 * Cout * Cin * ksize * ksize * N * H * W, Cout, Cin, H, W, N);
       e = conv_dgrad(View{const_cast<float*>(dz), Cout, 0}, N, H, W, Cout, wp, Cin, ksize, epi,
                      View{const_cast<float*>(mask), mask_stride, 0}, View{dx, dx_stride, 0}, s);
+    }
     return hip_status(e, "dn_conv2d_backward_data");
   });
 }
@@ -254,9 +262,11 @@ dn_status dn_deconv2x2_forward(const float* x, int N, int H, int W, int Cin, con
     hipStream_t s = (hipStream_t)stream;
     float* wp = static_cast<float*>(pack_ws);
     hipError_t e = pack_deconv_fwd(w, Cin, Cout, wp, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess) {
+      const OpTimer timer(s, "deconv", 2.0 * N * H * W * Cin * Cout * 4, Cin, Cout, H, W, N);
       e = deconv_forward(View{const_cast<float*>(x), Cin, 0}, N, H, W, Cin, wp, b, Cout,
                          View{y, y_stride, y_off}, s);
+    }
     return hip_status(e, "dn_deconv2x2_forward");
   });
 }
@@ -318,10 +328,12 @@ dn_status dn_deconv2x2_backward_data(const float* dy, int dy_stride, int N, int 
     hipStream_t s = (hipStream_t)stream;
     float* wp = static_cast<float*>(pack_ws);
     hipError_t e = pack_deconv_dgrad(w, Cout, Cin, wp, s);
-    if (e == hipSuccess)
+    if (e == hipSuccess) {
+      const OpTimer timer(s, "deconv_dgrad", 2.0 * N * H * W * Cin * Cout * 4, Cout, Cin, H, W, N);
       e = deconv_dgrad(View{const_cast<float*>(dy), dy_stride, 0}, N, H, W, Cout, wp, Cin,
                        View{const_cast<float*>(mask), Cin, 0}, mask ? EPI_MASK : EPI_PLAIN,
                        View{dx, Cin, 0}, s);
+    }
     return hip_status(e, "dn_deconv2x2_backward_data");
   });
 }

@@ -15,6 +15,7 @@
 // Data layout: activations NHWC fp32 (channels contiguous), weights in the reference's
 // PyTorch layout read through a strided view (no repacking pass).
 #include <cstdlib>
+#include <string>
 
 #include "conv_epi.h"
 
@@ -1055,7 +1056,10 @@ static hipError_t run_fwd(const FwdArgs& a, hipStream_t s) {
   const int tx = (a.OW + C::TW - 1) / C::TW, ty = (a.OH + C::TH - 1) / C::TH;
   const int nz = a.zc ? (a.NOUT + a.zc - 1) / a.zc : ((a.out_layout == OUT_UP2 && GATHER != G_UP) ? 4 : 1);
   dim3 grid(tx * ty, a.N, nz);
-  prof_kernel("k_fwd");
+  static const char* const gn[4] = {"G_C3", "G_C1", "G_DN2", "G_UP"};
+  static const std::string kn = std::string("k_fwd<") + gn[GATHER] + "," + std::to_string(NT) + "," +
+                                std::to_string(MT) + ">";  // (the instance, as rocprofv3 names it)
+  prof_kernel(kn.c_str());
   hipLaunchKernelGGL((k_fwd<GATHER, NT, MT>), grid, dim3(256), 0, s, a, HeadArgs{});
   return hipGetLastError();
 }
@@ -1220,11 +1224,13 @@ hipError_t launch_fwd(int gather, const FwdArgs& a, hipStream_t s) {
   const bool small = big_tiles < 1024;
   if (gather == G_C3) {
     const int mt = pick_mt(nt, a, 1, nt != 9);
+    if (nt == 2) return mt == 4 ? run_fwd<G_C3, 2, 4>(a, s) : mt == 2 ? run_fwd<G_C3, 2, 2>(a, s) : run_fwd<G_C3, 2, 1>(a, s);
     if (nt == 3) return mt == 4 ? run_fwd<G_C3, 3, 4>(a, s) : mt == 2 ? run_fwd<G_C3, 3, 2>(a, s) : run_fwd<G_C3, 3, 1>(a, s);
     if (nt == 6) return mt == 4 ? run_fwd<G_C3, 6, 4>(a, s) : mt == 2 ? run_fwd<G_C3, 6, 2>(a, s) : run_fwd<G_C3, 6, 1>(a, s);
     if (nt == 9) return mt == 2 ? run_fwd<G_C3, 9, 2>(a, s) : run_fwd<G_C3, 9, 1>(a, s);
   } else if (gather == G_C1) {
     if (nt == 1) return run_fwd<G_C1, 1, 4>(a, s);
+    if (nt == 2) return small ? run_fwd<G_C1, 2, 1>(a, s) : run_fwd<G_C1, 2, 4>(a, s);
     if (nt == 3) return small ? run_fwd<G_C1, 3, 1>(a, s) : run_fwd<G_C1, 3, 4>(a, s);
     if (nt == 6) return small ? run_fwd<G_C1, 6, 1>(a, s) : run_fwd<G_C1, 6, 2>(a, s);
   } else if (gather == G_UP) {

@@ -17,6 +17,7 @@
 //   ds_read_b128 lane groups for every tap offset.  (The unswizzled 80-B rows of round 2 were
 //   2-way on a third of those groups: SQ_LDS_BANK_CONFLICT 47 % of the LDS-active cycles.)
 #include <cstdlib>
+#include <string>
 
 #include "conv_epi.h"
 #include "dn_internal.h"
@@ -384,6 +385,10 @@ static hipError_t run_bf16(const FwdArgs& a, hipStream_t s) {
   using C = BCfg<NT, MT, K3>;
   const int tx = (a.OW + C::TW - 1) / C::TW, ty = (a.OH + C::TH - 1) / C::TH;
   const int nz = a.out_layout == OUT_UP2 ? 4 : 1;
+  static const std::string kn = "k_fwd_bf16<" + std::to_string(NT) + "," + std::to_string(MT) +
+                                (K3 ? ",true" : ",false");
+  static const std::string knb = kn + ",true>", knf = kn + ">";  // (rocprofv3 names)
+  prof_kernel(a.in_bf16 ? knb.c_str() : knf.c_str());
   if (a.in_bf16)
     hipLaunchKernelGGL((k_fwd_bf16<NT, MT, K3, true>), dim3(tx * ty, a.N, nz), dim3(256), 0, s, a);
   else

@@ -190,6 +190,34 @@ def test_ran_kernel_label_and_count():
                 pass
 
 
+def test_ran_kernel_takes_the_op_names_to_look_for():
+    fwd1 = rec("fwd1", "k_fwd<G_C1,3,1>")
+    # the default set does not know the 1x1 / deconv records
+    with pytest.raises(AssertionError, match="expected one GEMM launch record"):
+        with ran_kernel(FakeLib([fwd1])):
+            pass
+    with ran_kernel(FakeLib([rec("pack", ""), fwd1]), "k_fwd<G_C1,3,1>", ops=("fwd1",)) as ran:
+        pass
+    assert ran.kernel == "k_fwd<G_C1,3,1>" and ran.record["op"] == "fwd1"
+    with ran_kernel(FakeLib([rec("deconv", "k_fwd<G_UP,6,4>")]), "k_fwd<G_UP,", ops="deconv") as ran:
+        pass
+    assert ran.record["op"] == "deconv"
+    # a record of the default set is NOT counted once the caller names its own set ...
+    with pytest.raises(AssertionError, match=r"record of \('deconv_dgrad',\)"):
+        with ran_kernel(FakeLib([rec("fwd3", "k_fwd<G_C3,6,4>")]), ops=("deconv_dgrad",)):
+            pass
+    # ... two records of the named set fail, and the prefix is still checked
+    with pytest.raises(AssertionError):
+        with ran_kernel(FakeLib([fwd1, rec("dgrad1", "k_fwd<G_C1,6,1>")]), ops=("fwd1", "dgrad1")):
+            pass
+    with pytest.raises(AssertionError, match="expected 'k_fwd<G_C1,6,'"):
+        with ran_kernel(FakeLib([fwd1]), "k_fwd<G_C1,6,", ops=("fwd1",)):
+            pass
+    with pytest.raises(AssertionError, match="no op name"):
+        with ran_kernel(FakeLib([fwd1]), ops=()):
+            pass
+
+
 def test_ran_kernel_disables_the_profiler_when_the_call_raises():
     lib = FakeLib([])
     with pytest.raises(RuntimeError, match="boom"):

@@ -109,10 +109,12 @@ class _Ran:
 
 
 @contextlib.contextmanager
-def ran_kernel(lib, prefix=None):
+def ran_kernel(lib, prefix=None, ops=GEMM_OPS):
     """Runs the body under the launch profiler and asserts that it took exactly one GEMM record
-    (fwd3 / dgrad3 / wgrad3) whose kernel label starts with `prefix` (None: any label; the
-    yielded object's .kernel / .record hold it after the block)."""
+    (an op of `ops`; by default fwd3 / dgrad3 / wgrad3) whose kernel label starts with `prefix`
+    (None: any label; the yielded object's .kernel / .record hold it after the block)."""
+    ops = (ops,) if isinstance(ops, str) else tuple(ops)
+    assert ops, "ran_kernel: no op name to look for"
     out = _Ran()
     lib.profile_ops(True)
     try:
@@ -120,8 +122,8 @@ def ran_kernel(lib, prefix=None):
         recs = lib.profile_ops_take()
     finally:
         lib.profile_ops(False)
-    gemm = [r for r in recs if r["op"] in GEMM_OPS]
-    assert len(gemm) == 1, f"expected one GEMM launch record, got {recs}"
+    gemm = [r for r in recs if r["op"] in ops]
+    assert len(gemm) == 1, f"expected one GEMM launch record of {ops}, got {recs}"
     out.record, out.kernel = gemm[0], gemm[0]["kernel"]
     assert out.kernel, f"the GEMM record carries no kernel label: {gemm[0]}"
     if prefix is not None:
