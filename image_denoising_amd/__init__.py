@@ -6,7 +6,7 @@ behind the C-ABI of libdenoise_hip.so (include/denoise_hip.h).
 """
 from .adapter import DenoiserWithAdapter, OutputAdapter  # noqa: F401
 from .arch_unet import UNet, reference_init  # noqa: F401
-from .finetune import FinetuneTrainer  # noqa: F401
+from .data import DevicePatchSampler, epoch_plan  # noqa: F401
 from .improved_unet import ImprovedUNet  # noqa: F401
 from .n2n import (AugmentNoise, generate_mask_pair, generate_subimages,  # noqa: F401
                   n2n_loss, n2n_subsample)
@@ -16,3 +16,13 @@ from .trainer import N2NTrainer, StructureTrainer, SupervisedTrainer  # noqa: F4
 from .util import L1FFT, Structure_loss  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # FinetuneTrainer on first use: `python -m image_denoising_amd.finetune` then executes the
+    # module once, not a second copy beside one this package already imported
+    if name == "FinetuneTrainer":
+        from .finetune import FinetuneTrainer
+
+        return FinetuneTrainer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -19,10 +19,11 @@ CSRC = os.path.join(PKG, "csrc")
 TAG = os.environ.get("DN_BUILD_TAG", "")
 BUILD = os.path.join(PKG, "_objs" + (f"_{TAG}" if TAG else ""))
 LIB = os.path.join(PKG, "libdenoise_hip" + (f"_{TAG}" if TAG else "") + ".so")
-SOURCES = ["conv.hip", "conv_bf16.hip", "conv_x6.hip", "head_x6.hip", "deconv_x6.hip", "upconv_x6.hip", "conv_w6.hip", "wgrad_x6p.hip", "elementwise.hip", "guard.hip", "first_layer.hip", "eval.hip", "adapter.hip", "memory.hip", "fft_loss.hip", "iunet_ops.hip", "wgrad_route.cpp", "exec_common.cpp", "unet.cpp",
+SOURCES = ["conv.hip", "conv_bf16.hip", "conv_x6.hip", "head_x6.hip", "deconv_x6.hip", "upconv_x6.hip", "conv_w6.hip", "wgrad_x6p.hip", "elementwise.hip", "guard.hip", "first_layer.hip", "eval.hip", "adapter.hip", "memory.hip", "fft_loss.hip", "iunet_ops.hip", "patch_sample.hip", "wgrad_route.cpp", "exec_common.cpp", "unet.cpp",
            "iunet.cpp", "resnet.cpp", "capi_net.cpp", "capi_train.cpp", "capi_ops.cpp", "capi_blocks.cpp",
-           "capi_eval.cpp", "capi_adapter.cpp", "profile.cpp"]
+           "capi_eval.cpp", "capi_adapter.cpp", "capi_data.cpp", "profile.cpp"]
 HEADERS = ["dn_internal.h", "wgrad_route.h", "block_reduce.h", "conv_epi.h", "x6_core.h", "x6_tile.h", "philox.h", "exec_common.h", "capi_common.h", "unet.h", "iunet.h", "iunet_ops.h", "resnet.h"]
+API_HEADERS = ["denoise_hip.h", "denoise_hip_data.h"]  # include/: the C-ABI
 ARCH = os.environ.get("DN_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
@@ -50,7 +51,7 @@ def source_hash() -> str:
     for f in sorted(FILE_FLAGS):
         h.update(f.encode() + b":" + " ".join(FILE_FLAGS[f]).encode() + b"\0")
     paths = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    paths.append(os.path.join(ROOT, "include", "denoise_hip.h"))
+    paths += [os.path.join(ROOT, "include", h) for h in API_HEADERS]
     for p in paths:
         h.update(os.path.basename(p).encode() + b"\0")
         with open(p, "rb") as f:
@@ -60,7 +61,7 @@ def source_hash() -> str:
 
 def _newest_header() -> float:
     paths = [os.path.join(CSRC, h) for h in HEADERS]
-    paths.append(os.path.join(ROOT, "include", "denoise_hip.h"))
+    paths += [os.path.join(ROOT, "include", h) for h in API_HEADERS]
     return max(os.path.getmtime(p) for p in paths)
 
 

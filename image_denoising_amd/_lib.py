@@ -1,4 +1,4 @@
-"""ctypes binding of libdenoise_hip.so (include/denoise_hip.h).
+"""ctypes binding of libdenoise_hip.so (include/denoise_hip.h, include/denoise_hip_data.h).
 
 The product path has no fallback: if the HIP library is missing or fails to load, importing
 anything that computes raises.  Tensors cross the boundary as raw device pointers; the HIP
@@ -208,6 +208,12 @@ SIGNATURES = {
                               _F, c_void_p]),
 }
 
+# include/denoise_hip_data.h: the input side (the device patch sampler), same library
+DATA_SIGNATURES = {
+    "dn_patch_sample": (c_int, [_F, _F, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                c_uint64, c_uint64, c_uint64, c_void_p, _F, _F, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -224,7 +230,7 @@ def lib() -> ctypes.CDLL:
         if L.dn_abi_version() != ABI_VERSION:  # the argument lists below are revision 5's
             raise RuntimeError(f"{LIB_PATH}: ABI revision {L.dn_abi_version()}, the binding "
                                f"expects {ABI_VERSION} (include/denoise_hip.h DN_ABI_VERSION)")
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **DATA_SIGNATURES}.items():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

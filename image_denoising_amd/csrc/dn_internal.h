@@ -528,4 +528,12 @@ hipError_t launch_memadapter_feature_adjoint(const float* base, const float* dfe
 hipError_t launch_hann_blend(const float* pred, const float* hann, const int* ys, const int* xs,
                              int ny, int nx, int C, int H, int W, int P, float* out, hipStream_t s);
 
+// patch_sample.hip: paired random crops / 255 from device-resident image pools
+hipError_t launch_patch_sample(const float* clean_pool, const float* noisy_pool, long pool_elems,
+                               const long* table, int M, int C, const int* img_idx, int N, int ps,
+                               unsigned long long seed, unsigned long long offset,
+                               unsigned long long item_base, const int* origins_in,
+                               float* clean_out, float* noisy_out, int* origins_out,
+                               hipStream_t s);
+
 }  // namespace dn

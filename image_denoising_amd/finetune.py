@@ -15,8 +15,12 @@ With DenoiserWithAdapter(freeze_base=False, use_no_grad_for_base=False) the base
     dB       = base backward(dbase)              dn_<family>_backward_prec
     Adam(B, dB / world)                          dn_adam_step
 
-No host synchronisation inside the step.  The patch loader (`DenoisePatchDataset`,
-finetune.py:100-150) is host code, as in the reference.
+No host synchronisation inside the step.  `DenoisePatchDataset` restates the reference's host
+loader (finetune.py:100-150); the training command feeds the step from the device-resident
+sampler instead (data.DevicePatchSampler, one dn_patch_sample launch per batch):
+
+    python -m image_denoising_amd.finetune --data_dir D --pretrained_ckpt base.pth [--arch UNet]
+        [--seed 0] [--precision fp32|fp32_x6] [--base_bf16]        (finetune.py:221-345's loop)
 """
 from __future__ import annotations
 
@@ -380,3 +384,148 @@ class FinetuneTrainer(_AdapterStepBase):
         ad._run_backward(noisy, b["base"], dpred, self.grad)
         self._update(loss=loss3[-1] if self.guard is not None else None)
         return loss3
+
+
+def parse_args(argv=None):
+    """finetune.py:23-81, same names and defaults (parse_known_args there too), plus --seed,
+    --precision and --base_bf16.  --num_workers and --gpu_devices are accepted and ignored: the
+    loader is the device sampler, and the process uses the current device."""
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m image_denoising_amd.finetune")
+    ap.add_argument("--data_dir", type=str, required=True,
+                    help="B-domain root. Must contain clean/ and noise/ subfolders.")
+    ap.add_argument("--pretrained_ckpt", type=str, required=True,
+                    help="Checkpoint of the base model trained on A-domain.")
+    ap.add_argument("--arch", type=str, default="UNetImproved",
+                    choices=["UNet", "RESNET", "UNetImproved"])
+    ap.add_argument("--save_model_path", type=str, default="./results_ft")
+    ap.add_argument("--log_name", type=str, default="UNetImproved_adapter_ft")
+    ap.add_argument("--gpu_devices", default="0", type=str)
+    ap.add_argument("--parallel", action="store_true")
+    ap.add_argument("--n_feature", type=int, default=48)
+    ap.add_argument("--n_channel", type=int, default=1)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--n_epoch", type=int, default=20)
+    ap.add_argument("--batchsize", type=int, default=4)
+    ap.add_argument("--num_workers", type=int, default=4)
+    ap.add_argument("--adapter_hidden", type=int, default=16)
+    ap.add_argument("--lambda_grad", type=float, default=0.1)
+    ap.add_argument("--save_every", type=int, default=1)
+    ap.add_argument("--patch_size", type=int, default=128)
+    ap.add_argument("--patches_per_image", type=int, default=16)
+    ap.add_argument("--seed", type=int, default=0,
+                    help="Seeds the adapter's initialisation, the epoch shuffles and the crops.")
+    ap.add_argument("--precision", type=str, default="fp32", choices=["fp32", "fp32_x6"],
+                    help="set_precision of the base.")
+    ap.add_argument("--base_bf16", action="store_true",
+                    help="set_inference_precision('bf16') of the frozen base (UNet).")
+    args, _ = ap.parse_known_args(argv)
+    if args.parallel:
+        ap.error("--parallel (nn.DataParallel) is not built: start one process per GPU with "
+                 "torchrun and drive FinetuneTrainer(model, distributed=True) from "
+                 "DevicePatchSampler.batches(epoch, batch, world, rank)")
+    if args.base_bf16 and args.arch != "UNet":
+        ap.error("--base_bf16: only UNet has the bf16 inference plan")
+    return args
+
+
+def main(argv=None):
+    """The loop of finetune.py:221-345 on the device path: DevicePatchSampler.batches feeds
+    FinetuneTrainer; the adapter is initialised under torch.manual_seed(--seed), the same seed
+    drives the sampler.  The host reads a loss only where a line is printed, and the epoch's
+    stacked losses once at its end (the mean L1).  Returns dict(losses = every step's [loss_l1,
+    loss_grad, loss], mean_l1 per epoch, checkpoints = the files written, psnr = {epoch: [dB per
+    validation image]})."""
+    import datetime
+    import time
+
+    from PIL import Image
+
+    from .checkpoint import save_finetune_checkpoint
+    from .data import DevicePatchSampler
+    from .evaluation import _device, psnr_device, validation_denoise
+    from .evaluation_adapter import denoise
+
+    opt = parse_args(argv)
+    dev = _device()
+    systime = datetime.datetime.now().strftime("%Y-%m-%d-%H-%M")
+    sampler = DevicePatchSampler.from_dir(opt.data_dir, opt.patch_size, opt.patches_per_image,
+                                          seed=opt.seed, device=dev)
+    print(f"B-domain: {len(sampler.sizes)} images, {opt.patches_per_image} patches/image/epoch → "
+          f"{len(sampler)} samples/epoch.")
+    valid = validation_denoise(opt.data_dir)
+
+    base = build_base_model(opt.arch, opt.n_channel, opt.n_feature)
+    missing, unexpected = load_base_weights(base, opt.pretrained_ckpt)
+    if missing:
+        print(f"[Warning] Missing keys when loading base model: {missing}")
+    if unexpected:
+        print(f"[Warning] Unexpected keys when loading base model: {unexpected}")
+    print(f"Loaded base weights from {opt.pretrained_ckpt}")
+    base.set_precision(opt.precision)
+    if opt.base_bf16:
+        base.set_inference_precision("bf16")
+    torch.manual_seed(opt.seed)
+    model = DenoiserWithAdapter(base, in_channels=opt.n_channel, hidden_channels=opt.adapter_hidden,
+                                freeze_base=True, use_no_grad_for_base=True).to(dev)
+    trainer = FinetuneTrainer(model, lr=opt.lr, lambda_grad=opt.lambda_grad, distributed=False)
+
+    print(f"==> Start finetuning with adapter + patches. Num epochs={opt.n_epoch}, "
+          f"batchsize={opt.batchsize}, lr={opt.lr}, lambda_grad={opt.lambda_grad}, "
+          f"patch_size={opt.patch_size}, patches_per_image={opt.patches_per_image}")
+    out_dir = os.path.join(opt.save_model_path, opt.log_name)
+    steps = sampler.steps_per_epoch(opt.batchsize)
+    res = dict(losses=[], mean_l1=[], checkpoints=[], psnr={})
+    for epoch in range(1, opt.n_epoch + 1):
+        model.train()
+        epoch_st = time.time()
+        losses = []
+        for i, (clean, noisy) in enumerate(sampler.batches(epoch, opt.batchsize), start=1):
+            loss3 = trainer.train_step(clean, noisy)
+            losses.append(loss3)
+            if i % 10 == 0 or i == steps:
+                l1, lg, lt = loss3.tolist()
+                print(f"Epoch [{epoch}/{opt.n_epoch}] Iter [{i}/{steps}] "
+                      f"L1={l1:.6f} Grad={lg:.6f} Total={lt:.6f}")
+        ep = torch.stack(losses).cpu()  # the epoch's one read of every step's loss
+        res["losses"].extend(ep.tolist())
+        mean_loss = float(np.mean(ep[:, 0].double().numpy()))
+        res["mean_l1"].append(mean_loss)
+        print(f"End of epoch {epoch}, mean L1 loss={mean_loss:.6f}, "
+              f"time={time.time() - epoch_st:.2f}s")
+
+        if epoch % opt.save_every == 0 or epoch == opt.n_epoch:
+            path = save_finetune_checkpoint(
+                model, os.path.join(out_dir, f"epoch_adapter_{epoch:03d}.pth"))
+            print(f"Checkpoint saved to {path}")
+            res["checkpoints"].append(path)
+            model.eval()
+            save_dir = os.path.join(out_dir, f"val_{systime}_ep{epoch:03d}")
+            os.makedirs(save_dir, exist_ok=True)
+            res["psnr"][epoch] = []
+            for i, (clean_u8, noisy_u8) in enumerate(zip(valid[0], valid[1])):
+                clean_name = os.path.basename(valid[2][i]).split(".")[0]
+                noisy_name = os.path.basename(valid[3][i]).split(".")[0]
+                p8 = denoise(model, noisy_u8)
+                c8 = torch.from_numpy(clean_u8).to(dev)
+                c8 = c8.unsqueeze(0) if c8.dim() == 2 else c8.permute(2, 0, 1).contiguous()
+                # finetune.py:165-173: mse == 0 -> 99.0
+                psnr = 99.0 if torch.equal(p8, c8) else float(psnr_device(p8, c8).cpu())
+                res["psnr"][epoch].append(psnr)
+                print(f"Val ep{epoch} [{i + 1}/{len(valid[0])}] {noisy_name}: psnr={psnr:.2f} dB")
+                if i == 0:
+                    pred = p8.cpu().numpy()
+                    vis = pred[0] if pred.shape[0] == 1 else np.transpose(pred, (1, 2, 0))
+                    Image.fromarray(clean_u8).convert("L").save(
+                        os.path.join(save_dir, f"{clean_name}_clean.png"))
+                    Image.fromarray(noisy_u8).convert("L").save(
+                        os.path.join(save_dir, f"{noisy_name}_noisy.png"))
+                    Image.fromarray(vis).convert("L").save(
+                        os.path.join(save_dir, f"{noisy_name}_denoised_ep{epoch:03d}.png"))
+    print("Finetuning complete.")
+    return res
+
+
+if __name__ == "__main__":
+    main()
