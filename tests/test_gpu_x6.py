@@ -64,14 +64,17 @@ def _forward(x, w, b, act, x6):
     (48, 48, 2, 32, 32), (48, 96, 1, 20, 36), (96, 96, 2, 16, 16), (96, 96, 2, 64, 64),
     (144, 96, 2, 16, 32), (99, 96, 2, 32, 32), (97, 48, 1, 8, 8), (3, 48, 2, 32, 32),
     (96, 96, 64, 32, 32), (48, 48, 8, 4, 4),
-    # >= 512 16x16 tiles: the pipelined 8-wave kernel (k_c3x6p)
+    # >= 512 8x16 tiles at exactly 96 / 48 outputs: the Winograd kernel k_c3w6 (tail 0 / 2 / 2);
+    # 3 -> 48 is not float4-addressable and stays on the 4-wave k_c3x6.  (Which instantiation a
+    # shape runs is asserted in test_gpu_x6_edges.py and test_gpu_x6_direct_edges.py, not here.)
     (96, 96, 8, 128, 128), (48, 48, 8, 128, 128), (144, 96, 8, 128, 128), (3, 48, 2, 256, 256),
-    # pipelined with a partial last chunk packed over fewer stages (x6_tail_mode 1 / 2)
+    # k_c3w6 with a partial last chunk packed over fewer stages (x6_tail_mode 1 / 2)
     (100, 96, 2, 256, 256), (36, 48, 4, 128, 128), (80, 96, 8, 128, 128), (16, 48, 8, 128, 128),
-    # 32 outputs (ImprovedUNet RDB growth convs): 4-wave and pipelined (+ tail)
+    # 32 outputs (ImprovedUNet RDB growth convs): the small-grid 3-slot ring k_c3x6h<2,0,1,3>,
+    # then 512 tiles on k_c3x6h<2,2,2> (a 16-channel tail chunk)
     (48, 32, 2, 32, 32), (144, 32, 1, 24, 40), (80, 32, 8, 128, 128), (112, 32, 8, 128, 128),
-    # ImprovedUNet routes on large grids: K 48..79 at 32 outputs, zero-padded 32-wide K (88,
-    # 120), and 72 -> 24 (the pipelined / half kernels, not only the 4-wave small-grid ones)
+    # ImprovedUNet routes on large grids (k_c3x6h<2,T,2>): K 48..79 at 32 outputs, zero-padded
+    # 32-wide K (88, 120), and 72 -> 24
     (48, 32, 8, 128, 128), (88, 32, 8, 128, 128), (120, 32, 8, 128, 128), (72, 24, 8, 128, 128),
 ])
 @pytest.mark.parametrize("act", [0, 1])
@@ -116,9 +119,11 @@ def _dgrad(dz, w, cin, mode, mask, base, x6):
 @pytest.mark.parametrize("cin,cout,N,H,W", [
     (48, 48, 2, 32, 32), (96, 96, 2, 16, 16), (144, 96, 2, 16, 16), (48, 96, 2, 8, 8),
     (96, 48, 1, 20, 36), (144, 96, 1, 64, 32),
-    (96, 96, 8, 128, 128), (144, 96, 3, 128, 112), (48, 48, 8, 128, 128),  # pipelined kernel
+    # large grids into 96 / 48 channels or 48-channel blocks: the Winograd kernel k_c3w6
+    (96, 96, 8, 128, 128), (144, 96, 3, 128, 112), (48, 48, 8, 128, 128),
     (96, 80, 8, 128, 128), (48, 16, 8, 128, 128), (96, 4, 8, 128, 128),  # ... with a tail chunk
-    (32, 96, 2, 32, 32), (32, 48, 8, 128, 128),  # 32 outputs
+    # 32 outputs: k_c3x6h<2,0,1,3> (small grid) and k_c3x6h<2,2,2> (512 tiles, K = 48)
+    (32, 96, 2, 32, 32), (32, 48, 8, 128, 128),
     # ImprovedUNet shapes: final conv (K = out_nc), RDB growth convs (K = 32, wide outputs)
     (24, 3, 1, 32, 32), (24, 1, 2, 32, 32), (144, 32, 1, 16, 16), (112, 32, 1, 16, 16),
     (80, 32, 2, 16, 16), (120, 32, 1, 32, 32), (72, 24, 1, 32, 32),

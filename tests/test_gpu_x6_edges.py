@@ -16,7 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from x6_edge_util import assert_regions, guarded, ran_kernel
+from x6_edge_util import assert_regions, gemm_flops, guarded, ran_kernel, run_dgrad, run_forward
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -51,10 +51,6 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
-def gemm_flops(rec):
-    return 2.0 * rec["K"] * rec["NOUT"] * 9 * rec["N"] * rec["H"] * rec["W"]
-
-
 # ---- forward -----------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=2)
 def _fwd_case(cin, cout, N, H, W):
@@ -69,35 +65,8 @@ def _fwd_case(cin, cout, N, H, W):
 
 def _forward(case, act, x_stride, y_stride, lead, x6, prefix=None):
     """one forward through the C-ABI on guarded views -> (y [N,H,W,cout] on the CPU, label)"""
-    _lib = L()
     x, w, b = case[:3]
-    N, H, W, cin = x.shape
-    cout = w.shape[0]
-    gx = guarded((N, H, W, cin), x_stride, lead, NAN, DEV)
-    gx.data.copy_(x)
-    gy = guarded((N, H, W, cout), y_stride, lead, NAN, DEV)
-    wg, bg = w.to(DEV), b.to(DEV)
-    if x6:
-        pk = _lib.scratch(_lib.lib().dn_conv2d_x6_pack_size(cin, cout, 0), DEV)
-        with ran_kernel(_lib, prefix) as ran:
-            _lib.call("dn_conv2d_forward_x6", gx.ptr, x_stride, N, H, W, cin, wg.data_ptr(),
-                      bg.data_ptr(), cout, act, gy.ptr, y_stride, pk.data_ptr(), pk.numel(), S())
-        rec = ran.record
-        assert (rec["op"], rec["K"], rec["NOUT"], rec["N"], rec["H"], rec["W"]) == \
-            ("fwd3", cin, cout, N, H, W), rec
-        assert rec["flops"] == gemm_flops(rec), rec
-        label = ran.kernel
-    else:
-        pk = _lib.scratch(_lib.lib().dn_conv2d_pack_size(cin, cout, 3, 0), DEV)
-        _lib.call("dn_conv2d_forward", gx.ptr, x_stride, N, H, W, cin, wg.data_ptr(),
-                  bg.data_ptr(), cout, 3, act, gy.ptr, y_stride, pk.data_ptr(), pk.numel(), S())
-        label = "fp32"
-    torch.cuda.synchronize()
-    gy.check(what=f"y ({label})")
-    gx.check(what=f"x ({label})")
-    y = gy.data.cpu()
-    assert bool(torch.isfinite(y).all()), f"{label}: non-finite or unwritten outputs"
-    return y, label
+    return run_forward(L(), x, w, b, act, x_stride, y_stride, lead, x6, prefix, DEV)
 
 
 def _fwd_ref(case, act):
@@ -197,49 +166,8 @@ def _dgrad_ref(case, mode):
 
 
 def _dgrad(case, mode, dx_stride, mask_stride, lead, x6, prefix=None):
-    _lib = L()
     dz, w, mask, base = case[:4]
-    N, H, W, cout = dz.shape
-    cin = w.shape[1]
-    gdz = guarded((N, H, W, cout), cout, lead, NAN, DEV)
-    gdz.data.copy_(dz)
-    gm = guarded((N, H, W, cin), mask_stride, lead, NAN, DEV)
-    gm.data.copy_(mask)
-    gdx = guarded((N, H, W, cin), dx_stride, lead, NAN, DEV)
-    base_full = None
-    if mode == "accum":  # a random base under the live channels AND the gap
-        g = torch.Generator().manual_seed(dx_stride)
-        base_full = torch.randn(N, H, W, dx_stride, generator=g)
-        base_full[..., :cin] = base
-        gdx.full.copy_(base_full)
-    wg = w.to(DEV)
-    name = "dn_conv2d_backward_data_x6" if x6 else "dn_conv2d_backward_data"
-    size = (_lib.lib().dn_conv2d_x6_pack_size(cin, cout, 1) if x6
-            else _lib.lib().dn_conv2d_pack_size(cin, cout, 3, 1))
-    pk = _lib.scratch(size, DEV)
-    args = [gdz.ptr, N, H, W, cout, wg.data_ptr(), cin]
-    if not x6:
-        args.append(3)
-    args += [gm.ptr if mode == "mask" else None, mask_stride, 1 if mode == "accum" else 0,
-             gdx.ptr, dx_stride, pk.data_ptr(), pk.numel(), S()]
-    if x6:
-        with ran_kernel(_lib, prefix) as ran:
-            _lib.call(name, *args)
-        rec = ran.record
-        assert (rec["op"], rec["K"], rec["NOUT"], rec["N"], rec["H"], rec["W"]) == \
-            ("dgrad3", cout, cin, N, H, W), rec
-        assert rec["flops"] == gemm_flops(rec), rec
-        label = ran.kernel
-    else:
-        _lib.call(name, *args)
-        label = "fp32"
-    torch.cuda.synchronize()
-    gdx.check(base=base_full, what=f"dx ({label}, {mode})")
-    gdz.check(what=f"dz ({label})")
-    gm.check(what=f"mask ({label})")
-    dx = gdx.data.cpu()
-    assert bool(torch.isfinite(dx).all()), f"{label}: non-finite or unwritten outputs"
-    return dx, label
+    return run_dgrad(L(), dz, w, mask, base, mode, dx_stride, mask_stride, lead, x6, prefix, DEV)
 
 
 def _dgrad_e32(case, mode):

@@ -1,6 +1,10 @@
-"""Helpers of tests/test_gpu_x6_edges.py (plain numpy / torch, checked on CPU tensors by
-tests/test_x6_edge_util_cpu.py): guarded strided NHWC buffers, per-region errors against a
-reference, and the launch profiler's record of the one GEMM kernel a call ran."""
+"""Helpers of tests/test_gpu_x6_edges.py and tests/test_gpu_x6_direct_edges.py (plain numpy /
+torch): guarded strided NHWC buffers, per-region errors against a reference and the launch
+profiler's record of the one GEMM kernel a call ran (these three checked on CPU tensors by
+tests/test_x6_edge_util_cpu.py); the operands of the exact cases, exact_operands /
+assert_bit_equal (checked by tests/test_x6_direct_edges_cpu.py); and the two op runners on
+guarded views, run_forward / run_dgrad, which need the GPU and are exercised by the two GPU
+files only."""
 import contextlib
 
 import numpy as np
@@ -51,7 +55,7 @@ class Guarded:
         for name, band, at in (("front", front, 0), ("back", back, self.off + self.inner)):
             bad = torch.nonzero(band != self.fill_bits)
             assert bad.numel() == 0, (
-                f"{what}: {name} guard band touched: {bad.numel()} floats, first at flat index "
+                f"{what}: {name} guard band touched: {bad.shape[0]} floats, first at flat index "
                 f"{at + int(bad[0])} (inner range [{self.off}, {self.off + self.inner}))")
         if self.stride > self.C:
             N, H, W, _ = self.shape
@@ -62,7 +66,7 @@ class Guarded:
                 want = _bits(base.to(self.buf.device))[..., self.C:]
                 bad = torch.nonzero(gap != want)
             assert bad.numel() == 0, (
-                f"{what}: gap channel touched: {bad.numel()} floats, first at (n, y, x, c) = "
+                f"{what}: gap channel touched: {bad.shape[0]} floats, first at (n, y, x, c) = "
                 f"{tuple(int(v) for v in bad[0][:3])} + ({self.C + int(bad[0][3])},)")
 
 
@@ -128,3 +132,127 @@ def ran_kernel(lib, prefix=None, ops=GEMM_OPS):
     assert out.kernel, f"the GEMM record carries no kernel label: {gemm[0]}"
     if prefix is not None:
         assert out.kernel.startswith(prefix), f"ran {out.kernel!r}, expected {prefix!r}..."
+
+
+# ---- the 3x3 ops through the C-ABI on guarded views ---------------------------------------------
+NAN = float("nan")
+
+
+def gemm_flops(rec):
+    return 2.0 * rec["K"] * rec["NOUT"] * 9 * rec["N"] * rec["H"] * rec["W"]
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def run_forward(lib, x, w, b, act, x_stride, y_stride, lead, x6, prefix=None, device="cuda"):
+    """One 3x3 forward (x NHWC, w OIHW, b on the CPU) through the C-ABI: x read at x_stride and y
+    written at y_stride, both `lead` floats into NaN-filled guarded buffers.  x6: the split-bf16
+    op, its one GEMM record checked against the shape and its label against `prefix`; else the
+    fp32 op.  Guard bands and gap channels of x and y must come back untouched and y finite.
+    -> (y [N, H, W, cout] on the CPU, label)"""
+    N, H, W, cin = x.shape
+    cout = w.shape[0]
+    gx = guarded((N, H, W, cin), x_stride, lead, NAN, device)
+    gx.data.copy_(x)
+    gy = guarded((N, H, W, cout), y_stride, lead, NAN, device)
+    wg, bg = w.to(device), b.to(device)
+    if x6:
+        pk = lib.scratch(lib.lib().dn_conv2d_x6_pack_size(cin, cout, 0), device)
+        with ran_kernel(lib, prefix) as ran:
+            lib.call("dn_conv2d_forward_x6", gx.ptr, x_stride, N, H, W, cin, wg.data_ptr(),
+                     bg.data_ptr(), cout, act, gy.ptr, y_stride, pk.data_ptr(), pk.numel(),
+                     _stream())
+        rec = ran.record
+        assert (rec["op"], rec["K"], rec["NOUT"], rec["N"], rec["H"], rec["W"]) == \
+            ("fwd3", cin, cout, N, H, W), rec
+        assert rec["flops"] == gemm_flops(rec), rec
+        label = ran.kernel
+    else:
+        pk = lib.scratch(lib.lib().dn_conv2d_pack_size(cin, cout, 3, 0), device)
+        lib.call("dn_conv2d_forward", gx.ptr, x_stride, N, H, W, cin, wg.data_ptr(),
+                 bg.data_ptr(), cout, 3, act, gy.ptr, y_stride, pk.data_ptr(), pk.numel(),
+                 _stream())
+        label = "fp32"
+    torch.cuda.synchronize()
+    gy.check(what=f"y ({label})")
+    gx.check(what=f"x ({label})")
+    y = gy.data.cpu()
+    assert bool(torch.isfinite(y).all()), f"{label}: non-finite or unwritten outputs"
+    return y, label
+
+
+def run_dgrad(lib, dz, w, mask, base, mode, dx_stride, mask_stride, lead, x6, prefix=None,
+              device="cuda"):
+    """One 3x3 data gradient (dz, mask, base NHWC, w OIHW on the CPU; mode plain / mask / accum)
+    through the C-ABI: dz dense, the mask read at mask_stride and dx written at dx_stride, all in
+    NaN-filled guarded buffers; accum starts from `base` under the live channels and a random
+    base in the gap, which must come back bit for bit.  -> (dx [N, H, W, cin] on the CPU, label)"""
+    N, H, W, cout = dz.shape
+    cin = w.shape[1]
+    gdz = guarded((N, H, W, cout), cout, lead, NAN, device)
+    gdz.data.copy_(dz)
+    gm = guarded((N, H, W, cin), mask_stride, lead, NAN, device)
+    gm.data.copy_(mask)
+    gdx = guarded((N, H, W, cin), dx_stride, lead, NAN, device)
+    base_full = None
+    if mode == "accum":  # a random base under the live channels AND the gap
+        g = torch.Generator().manual_seed(dx_stride)
+        base_full = torch.randn(N, H, W, dx_stride, generator=g)
+        base_full[..., :cin] = base
+        gdx.full.copy_(base_full)
+    wg = w.to(device)
+    name = "dn_conv2d_backward_data_x6" if x6 else "dn_conv2d_backward_data"
+    size = (lib.lib().dn_conv2d_x6_pack_size(cin, cout, 1) if x6
+            else lib.lib().dn_conv2d_pack_size(cin, cout, 3, 1))
+    pk = lib.scratch(size, device)
+    args = [gdz.ptr, N, H, W, cout, wg.data_ptr(), cin]
+    if not x6:
+        args.append(3)
+    args += [gm.ptr if mode == "mask" else None, mask_stride, 1 if mode == "accum" else 0,
+             gdx.ptr, dx_stride, pk.data_ptr(), pk.numel(), _stream()]
+    if x6:
+        with ran_kernel(lib, prefix) as ran:
+            lib.call(name, *args)
+        rec = ran.record
+        assert (rec["op"], rec["K"], rec["NOUT"], rec["N"], rec["H"], rec["W"]) == \
+            ("dgrad3", cout, cin, N, H, W), rec
+        assert rec["flops"] == gemm_flops(rec), rec
+        label = ran.kernel
+    else:
+        lib.call(name, *args)
+        label = "fp32"
+    torch.cuda.synchronize()
+    gdx.check(base=base_full, what=f"dx ({label}, {mode})")
+    gdz.check(what=f"dz ({label})")
+    gm.check(what=f"mask ({label})")
+    dx = gdx.data.cpu()
+    assert bool(torch.isfinite(dx).all()), f"{label}: non-finite or unwritten outputs"
+    return dx, label
+
+
+# ---- operands on which the split-bf16 arithmetic is exact ---------------------------------------
+def exact_operands(gen, x_shape, w_shape, nb=0):
+    """(x, w, b): x integers -4..4, w from {-2..2} / 8, b multiples of 1/8 in [-1, 1].  Each
+    value has at most 3 significant bits, so it is exact in bf16 (the low pieces of the split
+    are zero), every product is a multiple of 1/8 of magnitude at most 1, and a sum of
+    9 * K <= 9 * 4096 of them stays a multiple of 1/8 far below 2^24 / 8: exact in fp32 in any
+    order of summation."""
+    x = torch.randint(-4, 5, x_shape, generator=gen).float()
+    w = torch.randint(-2, 3, w_shape, generator=gen).float() / 8
+    b = torch.randint(-8, 9, (nb,), generator=gen).float() / 8
+    return x, w, b
+
+
+def assert_bit_equal(got, ref64, what=""):
+    """got (fp32) equals the fp64 reference bit for bit at every element (the sign of a zero
+    aside: x + 0.0 makes every zero +0)"""
+    got = torch.as_tensor(got)
+    ref = torch.as_tensor(ref64)
+    assert got.dtype == torch.float32 and ref.dtype == torch.float64 and got.shape == ref.shape
+    assert bool((ref.float().double() == ref).all()), f"{what}: the reference is not exact in fp32"
+    bad = torch.nonzero(_bits(got + 0.0) != _bits(ref.float() + 0.0))
+    assert bad.numel() == 0, (
+        f"{what}: {bad.shape[0]} elements differ from fp64, first at {tuple(int(v) for v in bad[0])}: "
+        f"{float(got[tuple(bad[0])])!r} vs {float(ref[tuple(bad[0])])!r}")
